@@ -1,9 +1,11 @@
 #!/usr/bin/env python3
 """bench.py — the MappingQC / coverage hot path on MI355X (BASELINE.json metric: Mreads/s + achieved HBM GB/s).
 
-Default workload = BASELINE.json configs[1]: MappingQC -wgs on a synthetic 30x WGS BAM (~6.2e8 2x150 bp PE reads, coordinate-sorted,
-zlib-6 BGZF, SURVEY.md §8(d) config 2 statistics; ~60 GB compressed, ~209 GB inflated) on one MI355X. The compressed image is resident
-in HBM when the timed region starts (the H2D time of the image is reported separately, and an end-to-end rate next to `value`).
+Workload = BASELINE.json configs[1]: MappingQC -wgs on a synthetic 30x WGS BAM (2x150 bp PE reads, coordinate-sorted, zlib-6 BGZF,
+SURVEY.md §8(d) config 2 statistics) on one MI355X. By default a step covers the first DEFAULT_READS reads of that file (a 32 M-read shard,
+~3 GB compressed: the generator writes it in seconds); `--reads 620000000` is the full file (~60 GB compressed, ~209 GB inflated; its
+generator alone takes ~5 min on 16 CPUs). The compressed image is resident in HBM when the timed region starts (the H2D time of the image
+is reported separately).
 A "step" is what `bin/MappingQC -wgs` does with the BAM, as ONE fused job (ngsqc_run_job): every BGZF member is inflated once (K1),
 records are indexed (K2), and the mapping_wgs scan (counters, insert-size histogram, chrX/chrY counts, OMIM-ROI depth scatter) plus the
 contamination pileup of the known common SNVs see every tile of the inflated stream while it is resident; then K6 (depth prefix sum,
@@ -16,10 +18,14 @@ histogram, half-depth count) and the result copies. The file is larger than HBM 
   --tool       mappingqc (default) | bedcoverage | bedlowcoverage   (configs[2]: exome-shaped BED over the same BAM)
   --ont        configs[4]: ONT-like long reads (N50 ~20 kb, CG-tag records), MappingQC -wgs -single_end shape
 
-Prints ONE JSON line (rank 0). Extra objects: roofline (dominant kernel by time), roofline_k1_stage, roofline_scan (SURVEY.md §8(d):
-t_scan = K2-K6 on resident inflated data, taken from one extra un-pipelined step), stage_ms, end_to_end, cpu_baseline (oracle, 1 thread,
-bounded sample), cpu_baseline_all_cores (same loop on every host core over the whole file; its additive counters and depth histogram are
-the parity check of the bench input: counters_match_gpu).
+  --dump-outputs DIR   after the timed steps, write what the last timed step returned to its caller as DIR/<name>.npy (float64)
+  --full       everything besides the headline (below); a plain run only sets up, warms up, times --steps steps and prints the line
+
+Prints ONE JSON line (rank 0): metric, value (Mreads/s of the timed steps), ms_per_step, config, stage_ms (HIP-event stage times of the timed
+steps), end_to_end (H2D of the image). With --full also: roofline (dominant kernel by time), roofline_k1_stage, roofline_scan (SURVEY.md §8(d):
+t_scan = K2-K6 on resident inflated data, taken from one extra un-pipelined step), cpu_baseline (oracle, 1 thread, bounded sample),
+cpu_baseline_all_cores (same loop on every host core over the whole file; its additive counters and depth histogram are the parity check of
+the bench input: counters_match_gpu), tools (configs[2]), ont (configs[4]), flavors, single_bam, collective, index and end_to_end from a file.
 """
 import argparse
 import importlib
@@ -39,7 +45,9 @@ for p in (ROOT, os.path.join(ROOT, "tests")):
 
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (/opt/skills/guides/MI355X_MICROARCH.md)
 FULL_READS = 620_000_000   # 30x of hg38 at 150 bp
+DEFAULT_READS = 32_000_000   # the default step: the first reads of that file (a plain run must stay within seconds of setup)
 BYTES_PER_READ_COMPRESSED = 98   # of the synthetic BAM (zlib-6)
+DUMP_BUDGET_BYTES = 63 << 20   # --dump-outputs: array bytes in all (64 MB with the .npy headers)
 
 
 def parse_args():
@@ -47,7 +55,7 @@ def parse_args():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
-    ap.add_argument("--reads", type=int, default=0, help="records per GPU per step (0 = the full 30x file when the host can hold it)")
+    ap.add_argument("--reads", type=int, default=0, help=f"records per GPU per step (0 = {DEFAULT_READS}; {FULL_READS} = the full 30x file, scaled down when the host cannot hold it)")
     ap.add_argument("--seed", type=int, default=20260821)
     ap.add_argument("--tool", default="mappingqc", choices=["mappingqc", "bedcoverage", "bedlowcoverage"])
     ap.add_argument("--min-baseq", type=int, default=0, help="bedlowcoverage: -min_baseq")
@@ -62,6 +70,9 @@ def parse_args():
                     "(all-gather of shard summaries, SUM all-reduce of counters and of the int32 difference array) instead of one BAM per rank")
     ap.add_argument("--image-cache", default="", help="keep / reuse the generated BAM image at this path (profiling passes on one box)")
     ap.add_argument("--all-ranks-on-device0", action="store_true", help="debug: map every rank to cuda:0")
+    ap.add_argument("--full", action="store_true", help="also the extra steps and legs: roofline / un-pipelined stage times, CPU baselines and parity, the coverage-tool, "
+                    "ONT and flavor legs, the one-BAM-over-N-GPUs leg, the collective check, end to end from a file")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write the arrays the last timed step returned as DIR/<name>.npy (float64)")
     return ap.parse_args()
 
 
@@ -127,6 +138,23 @@ def prefix_image(image, target_bytes):
     out = np.empty(pos + 28, dtype=np.uint8)
     out[:pos] = image[:pos]; out[pos:] = np.frombuffer(eof, dtype=np.uint8)
     return out
+
+
+def dump_outputs(dir_, arrays, seed):
+    """--dump-outputs: every array as <dir_>/<name>.npy in float64 (the counters are integers far below 2^53: exact), in the order given; an array
+    that does not fit what is left of DUMP_BUDGET_BYTES is replaced by a fixed, seeded sample of its rows (sorted row order). Returns {name: shape written}."""
+    os.makedirs(dir_, exist_ok=True)
+    left = DUMP_BUDGET_BYTES; written = {}
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        a = a.astype(np.float32 if a.dtype == np.float32 else np.float64)
+        if a.ndim and a.nbytes > left:
+            row = max(a.nbytes // max(a.shape[0], 1), 1)
+            k = min(a.shape[0], left // row)
+            a = a[np.sort(np.random.default_rng(seed).choice(a.shape[0], size=k, replace=False))]
+        np.save(os.path.join(dir_, name + ".npy"), a)
+        left -= a.nbytes; written[name] = list(a.shape)
+    return written
 
 
 
@@ -369,22 +397,25 @@ def main():
                 comm.close()
             comm = None; comm_note = comm_note or "a rank could not make the library's communicator: torch.distributed carries the collectives of this run"
 
-    # ---- workload size: the full 30x file when the host can hold the image (plus a private copy per rank for N > 1) ----
+    # ---- workload size: DEFAULT_READS of the 30x file unless --reads says otherwise; the full file only when the host can hold the image (plus a
+    # private copy per rank for N > 1) ----
     mode = 1 if args.ont else 0
     reads = args.reads
     size_note = ""
-    if reads <= 0:
-        if args.ont:
-            reads = 400_000    # ~14 GB inflated: a shard of the 40x ONT file (8e6 reads); long-CIGAR stress, not a capacity test
-            size_note = "shard of configs[4] (400 k of ~8e6 reads): the long-read generator is the limit, not the GPU"
-        else:
-            reads = FULL_READS
-            avail = host_memory_available()
-            need = reads * BYTES_PER_READ_COMPRESSED * (1.15 if world == 1 else 2.2)
-            if avail and need > 0.8 * avail:
-                reads = max(100_000_000, int(0.8 * avail / (BYTES_PER_READ_COMPRESSED * (1.15 if world == 1 else 2.2)) // 1_000_000 * 1_000_000))
-                reads = min(reads, FULL_READS)
-                size_note = f"scaled to {reads} reads: the host has {avail >> 30} GiB available for a {FULL_READS * BYTES_PER_READ_COMPRESSED >> 30} GiB image"
+    if reads <= 0 and args.ont:
+        reads = 400_000    # ~14 GB inflated: a shard of the 40x ONT file (8e6 reads); long-CIGAR stress, not a capacity test
+        size_note = "shard of configs[4] (400 k of ~8e6 reads): the long-read generator is the limit, not the GPU"
+    elif reads <= 0:
+        reads = DEFAULT_READS
+        size_note = f"the first {DEFAULT_READS} reads of the file, the default step"
+    if not args.ont and reads > 100_000_000:
+        avail = host_memory_available()
+        need = reads * BYTES_PER_READ_COMPRESSED * (1.15 if world == 1 else 2.2)
+        if avail and need > 0.8 * avail:
+            asked = reads
+            reads = max(100_000_000, int(0.8 * avail / (BYTES_PER_READ_COMPRESSED * (1.15 if world == 1 else 2.2)) // 1_000_000 * 1_000_000))
+            reads = min(reads, FULL_READS)
+            size_note = f"scaled to {reads} reads: the host has {avail >> 30} GiB available for a {asked * BYTES_PER_READ_COMPRESSED >> 30} GiB image"
 
     # ---- synthetic batch (generated by host threads, outside the timed region) ----
     # N > 1: rank 0 generates ONE image with all cores, the others map it from /dev/shm (every rank still holds and processes its own copy
@@ -470,6 +501,7 @@ def main():
     # ---- the step of each tool ----
     tool = args.tool
     aux = {}
+    last = {}   # the arrays the last step handed to its caller (--dump-outputs)
     if tool == "mappingqc":
         regs, _ = H.bed_regions(omim, refs, 3)
         mp = dict(mode=ngsqc.MODE_WGS, regions=regs, min_mapq=1, tid_x=tx, tid_y=ty, nonspecial=nonspecial)
@@ -478,11 +510,13 @@ def main():
             hh.drop_decoded()                                  # whole job from the compressed bytes, every step
             if sharded:
                 # one decode per shard for the mapping scan AND the contamination pileup (ngsqc_run_job_partial); site counts are summed over the shards
-                counters, _, _, _ = ngsqc.scan_mapping_sharded(hh, ngsqc.MODE_WGS, device=dev, comm=comm, regions=regs, min_mapq=1, tid_x=tx, tid_y=ty, nonspecial=nonspecial,
-                                                               sites=sites_arr, site_params=(1, 13, args.ont))
+                counters, gc, _, sc = ngsqc.scan_mapping_sharded(hh, ngsqc.MODE_WGS, device=dev, comm=comm, regions=regs, min_mapq=1, tid_x=tx, tid_y=ty, nonspecial=nonspecial,
+                                                                 sites=sites_arr, site_params=(1, 13, args.ont))
+                last.update(gc_reads=gc, site_counts=sc)
             else:
                 out = hh.run_job(mapping=mp, sites=sites_arr, site_params=(1, 13, args.ont))
                 counters = out["counters"]
+                last.update(gc_reads=out["gc_reads"], site_counts=out["site_counts"])
             roi_bases = int(counters[26]); usable_roi = int(counters[14])
             half = int(round(0.5 * usable_roi / roi_bases)) if roi_bases else 0
             hist, cov = hh.depth_stats(599, half)             # Histogram(0,599,5) input + half-depth count (Statistics.cpp:1185-1204)
@@ -491,6 +525,7 @@ def main():
                 aux["local_counters"] = np.asarray(counters, dtype=np.int64).copy()
                 # C1: RCCL reduce of the counter vectors over xGMI - the library's collective (ngsqc_comm_allreduce_counters); torch.distributed only with gloo
                 counters = comm.allreduce_counters(counters) if comm is not None else ngsqc.allreduce_counters(counters, device=dev)
+            last.update(counters=counters, depth_histogram=hist)
             return counters, hist
 
         def step():
@@ -508,9 +543,11 @@ def main():
             h.drop_decoded()
             if tool == "bedcoverage":
                 h.scan_depth(union_c, min_mapq=1, n_regions=n_union)
-                return h.region_sums(lines_c, n_lines=n_lines_c), None            # Statistics::avgCoverage: per-line depth sums
+                last["region_sums"] = h.region_sums(lines_c, n_lines=n_lines_c)   # Statistics::avgCoverage: per-line depth sums
+                return last["region_sums"], None
             h.scan_depth(union_c, min_mapq=1, min_baseq=args.min_baseq, n_regions=n_union)
-            return h.lowhigh_runs(lines_c, 20, is_high=False, saturate254=True, n_lines=n_lines_c, as_array=True), None   # BedLowCoverage -cutoff 20 (sweep mode)
+            last["low_coverage_runs"] = h.lowhigh_runs(lines_c, 20, is_high=False, saturate254=True, n_lines=n_lines_c, as_array=True)   # BedLowCoverage -cutoff 20 (sweep mode)
+            return last["low_coverage_runs"], None
 
     for _ in range(args.warmup):
         step()
@@ -534,11 +571,19 @@ def main():
         et = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(et, op=dist.ReduceOp.MAX)
         elapsed = float(et.item())
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        arrays = dict(last)
+        if "low_coverage_runs" in arrays:   # (ctypes array of ngsqc_run: line, start, end)
+            r_ = np.ctypeslib.as_array(arrays["low_coverage_runs"])
+            arrays["low_coverage_runs"] = np.stack([r_["line"], r_["start"], r_["end"]], axis=1)
+        dumped = dump_outputs(args.dump_outputs, arrays, args.seed)
+        mark("outputs written")
 
     # the collective against a second channel: every rank's local counter vector gathered with torch.distributed and combined on the host must be what the
     # library's all-reduce returned on this rank
     coll = None
-    if world > 1 and tool == "mappingqc" and not args.single_bam and "local_counters" in aux:
+    if args.full and world > 1 and tool == "mappingqc" and not args.single_bam and "local_counters" in aux:
         loc = torch.tensor(aux["local_counters"], dtype=torch.int64, device=dev)
         parts = [torch.empty_like(loc) for _ in range(world)]
         dist.all_gather(parts, loc)
@@ -569,7 +614,7 @@ def main():
         # ---- one extra un-pipelined step: K1 of a tile only starts when the previous tile is consumed, so the HIP-event stage times do
         # not overlap (t_scan = K2-K6 on resident inflated data) ----
         serial = None
-        if world == 1:
+        if args.full and world == 1:
             os.environ["NGSQC_PIPELINE"] = "0"
             ts = time.perf_counter(); step(); serial_wall = 1e3 * (time.perf_counter() - ts)
             serial = dict(h.timings(), wall_ms=serial_wall)
@@ -580,7 +625,7 @@ def main():
         # ---- one more extra step with every K1 kernel in line on ONE stream (NGSQC_K1_SERIAL): a launch's HIP-event interval is then the kernel's own
         # duration (in the pipelined steps two phase-1 launches and phase 2 / CRC of earlier chunks share the chip, their intervals overlap) ----
         iso = None
-        if world == 1:
+        if args.full and world == 1:
             os.environ["NGSQC_PIPELINE"] = "0"; os.environ["NGSQC_K1_SERIAL"] = "1"
             step(); iso = h.timings()
             del os.environ["NGSQC_PIPELINE"]; del os.environ["NGSQC_K1_SERIAL"]
@@ -614,18 +659,6 @@ def main():
                        "parallelism": (f"one BAM sharded over {world} GPU(s) by BGZF member range, 1 process/GPU; all-gather of shard summaries, "
                                        "SUM all-reduce of counters and of the int32 difference array (RCCL)") if args.single_bam
                                       else f"{world} BAM(s), one per GPU, 1 process/GPU, RCCL all-reduce of the counter vectors"},
-            "roofline": {"kernel": dom[0], "bound": "hbm", "limited_by": "instruction issue (VALU / LDS), not HBM: see profiles/r06_sq_counters.txt", "achieved": round(dom_gbs, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": round(dom_gbs / HBM_PEAK_GBS, 5), "traffic": None, "algorithmic_bytes_per_launch": int(dom[1]),
-                         "avg_launch_ms": round(dom[2], 4), "launches_per_step": k1_launches, "sum_launches_ms": round(dom[2] * k1_launches, 3),
-                         "isolated": iso is not None,
-                         "pipelined_interval_ms": {"huff_tokens_kernel": round(huff_ms / k1_launches, 4), "lz77_groups_kernel": round(lz_ms / k1_launches, 4),
-                                                   "note": "HIP-event intervals of the timed (pipelined) steps: co-resident launches on several streams, not kernel durations"},
-                         "isolated_launch_ms": None if iso is None else {"huff_tokens_kernel": round(iso["inflate_huff_ms"] / k1_launches, 4), "lz77_groups_kernel": round(iso["inflate_lz77_ms"] / k1_launches, 4)},
-                         "note": "avg_launch_ms: HIP events around the launch on its own stream in one extra step with the K1 kernels in line on one stream (the kernel alone on the "
-                                 "chip), so launches x avg_launch_ms <= ms_per_step. achieved = algorithmic bytes of a launch (compressed bytes in for phase 1, inflated bytes out for "
-                                 "phase 2) / that duration. DEFLATE decode is bit-serial per BGZF member: VALU-issue bound, not HBM bound (SURVEY.md §7)"},
-            "roofline_k1_stage": {"kernels": "huff_tokens_kernel + lz77_groups_kernel + crc32_kernel (chunk stream on three HIP streams)", "achieved": round(k1_gbs, 2), "unit": "GB/s",
-                                  "frac": round(k1_gbs / HBM_PEAK_GBS, 5), "algorithmic_bytes": c_bytes + u_bytes, "ms": round(infl_ms, 4)},
             "stage_ms": {"note": "sums of HIP-event intervals over the timed (pipelined) steps; index / scan / pileup overlap K1 of the next tile",
                          "inflate_huff": round(huff_ms, 4), "inflate_lz77": round(lz_ms, 4), "inflate_stage_wall": round(infl_ms, 4),
                          "index": round(avg("index_ms"), 4), "scan_kernels": round(avg("scan_kernel_ms"), 4), "scan_stage": round(avg("scan_ms"), 4),
@@ -637,6 +670,21 @@ def main():
                            "sequential_note": "ngsqc_open_memory (the caller owns the buffer: the H2D completes inside open), then one resident step"},
             "host": {"cores_reported": os.cpu_count(), "cores_usable": G.effective_cpus(), "generate_s": round(gen_s, 2)},
         }
+        if dumped is not None:
+            out["outputs_dumped"] = dumped
+        if args.full:
+            out["roofline"] = {"kernel": dom[0], "bound": "hbm", "limited_by": "instruction issue (VALU / LDS), not HBM: see profiles/r06_sq_counters.txt", "achieved": round(dom_gbs, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                               "frac": round(dom_gbs / HBM_PEAK_GBS, 5), "traffic": None, "algorithmic_bytes_per_launch": int(dom[1]),
+                               "avg_launch_ms": round(dom[2], 4), "launches_per_step": k1_launches, "sum_launches_ms": round(dom[2] * k1_launches, 3),
+                               "isolated": iso is not None,
+                               "pipelined_interval_ms": {"huff_tokens_kernel": round(huff_ms / k1_launches, 4), "lz77_groups_kernel": round(lz_ms / k1_launches, 4),
+                                                         "note": "HIP-event intervals of the timed (pipelined) steps: co-resident launches on several streams, not kernel durations"},
+                               "isolated_launch_ms": None if iso is None else {"huff_tokens_kernel": round(iso["inflate_huff_ms"] / k1_launches, 4), "lz77_groups_kernel": round(iso["inflate_lz77_ms"] / k1_launches, 4)},
+                               "note": "avg_launch_ms: HIP events around the launch on its own stream in one extra step with the K1 kernels in line on one stream (the kernel alone on the "
+                                       "chip), so launches x avg_launch_ms <= ms_per_step. achieved = algorithmic bytes of a launch (compressed bytes in for phase 1, inflated bytes out for "
+                                       "phase 2) / that duration. DEFLATE decode is bit-serial per BGZF member: VALU-issue bound, not HBM bound (SURVEY.md §7)"}
+            out["roofline_k1_stage"] = {"kernels": "huff_tokens_kernel + lz77_groups_kernel + crc32_kernel (chunk stream on three HIP streams)", "achieved": round(k1_gbs, 2), "unit": "GB/s",
+                                        "frac": round(k1_gbs / HBM_PEAK_GBS, 5), "algorithmic_bytes": c_bytes + u_bytes, "ms": round(infl_ms, 4)}
         if serial is not None:
             t_scan = serial["index_ms"] + serial["scan_ms"] + serial["finalize_ms"]   # K2-K6
             scan_gbs = scan_bytes / max(t_scan, 1e-9) / 1e6
@@ -650,38 +698,39 @@ def main():
                                            "depth_finalize": round(serial["finalize_ms"], 4), "contamination_pileup": round(serial["pileup_ms"], 4), "step_wall": round(serial["wall_ms"], 4)}
         # HBM traffic from the rocprofv3 PMC passes committed under profiles/ (separate --pmc runs of this command on a 48 M-read shard, K1 kernels in line):
         # raw FETCH_SIZE / WRITE_SIZE bytes per BGZF member (K1) or per record (scan stage), scaled to this run's launch
-        try:
-            per = {}
-            settings_ok = False
-            want = "k1_format=r06-word-per-trip-64B-lines tile_chunks=%s token_slots=%s" % (os.environ.get("NGSQC_TILE_CHUNKS", "8"), os.environ.get("NGSQC_TOKEN_SLOTS", "8"))
-            for ln in open(os.path.join(ROOT, "profiles", "r06_hbm_traffic_pmc.txt")):
-                if ln.startswith("# settings: "):
-                    settings_ok = want in ln   # (the per-member figures only describe launches of the same kernels under the same schedule)
-                if not settings_ok:
-                    continue
-                f = ln.rstrip("\n").split("\t")
-                if len(f) >= 4 and f[1] in ("FETCH_SIZE", "WRITE_SIZE") and f[2] in ("bytes_per_member", "bytes_per_record"):
-                    per[(f[0], f[1])] = float(f[3])
-            members_per_launch = int(h.n_blocks) / k1_launches
-            kname = dom[0].split(" ")[0]
-            if (kname, "FETCH_SIZE") in per and (kname, "WRITE_SIZE") in per:
-                fb, wb = per[(kname, "FETCH_SIZE")] * members_per_launch, per[(kname, "WRITE_SIZE")] * members_per_launch
-                out["roofline"]["traffic"] = int(fb + wb)
-                out["roofline"]["traffic_pmc"] = {"fetch_bytes_raw": int(fb), "write_bytes_raw": int(wb), "members_per_launch": int(members_per_launch),
-                                                  "source": "profiles/r06_hbm_traffic_pmc.txt (raw counter bytes per BGZF member x the members of this run's launch)",
-                                                  "ratio_to_algorithmic": round((fb + wb) / max(dom[1], 1), 2),
-                                                  "note": "raw FETCH_SIZE / WRITE_SIZE x 1024 B (no x2: the K1 accesses are 16-byte pieces of 64 different member streams per "
-                                                          "instruction, between the guide's narrow and wide regimes)"}
-            if "roofline_scan" in out:
-                keys = [k for k in per if k[0] in ("walk_scan_kernel", "scan_kernel", "index_count_kernel", "index_write_kernel", "index_guess_kernel")]
-                if keys:
-                    tot = sum(per[k] for k in keys) * n_rec
-                    out["roofline_scan"]["traffic"] = int(tot)
-                    out["roofline_scan"]["traffic_note"] = ("raw FETCH_SIZE + WRITE_SIZE of the K2 / scan kernels per record (profiles/r06_hbm_traffic_pmc.txt) x the records of the step; the "
-                                                            "kernels gather one or two 128-byte lines per record, so the guide's x2 for wide streams does not apply")
-        except OSError:
-            pass
-        if world == 1 and not args.no_cpu_baseline and tool == "mappingqc":
+        if args.full:
+            try:
+                per = {}
+                settings_ok = False
+                want = "k1_format=r06-word-per-trip-64B-lines tile_chunks=%s token_slots=%s" % (os.environ.get("NGSQC_TILE_CHUNKS", "8"), os.environ.get("NGSQC_TOKEN_SLOTS", "8"))
+                for ln in open(os.path.join(ROOT, "profiles", "r06_hbm_traffic_pmc.txt")):
+                    if ln.startswith("# settings: "):
+                        settings_ok = want in ln   # (the per-member figures only describe launches of the same kernels under the same schedule)
+                    if not settings_ok:
+                        continue
+                    f = ln.rstrip("\n").split("\t")
+                    if len(f) >= 4 and f[1] in ("FETCH_SIZE", "WRITE_SIZE") and f[2] in ("bytes_per_member", "bytes_per_record"):
+                        per[(f[0], f[1])] = float(f[3])
+                members_per_launch = int(h.n_blocks) / k1_launches
+                kname = dom[0].split(" ")[0]
+                if (kname, "FETCH_SIZE") in per and (kname, "WRITE_SIZE") in per:
+                    fb, wb = per[(kname, "FETCH_SIZE")] * members_per_launch, per[(kname, "WRITE_SIZE")] * members_per_launch
+                    out["roofline"]["traffic"] = int(fb + wb)
+                    out["roofline"]["traffic_pmc"] = {"fetch_bytes_raw": int(fb), "write_bytes_raw": int(wb), "members_per_launch": int(members_per_launch),
+                                                      "source": "profiles/r06_hbm_traffic_pmc.txt (raw counter bytes per BGZF member x the members of this run's launch)",
+                                                      "ratio_to_algorithmic": round((fb + wb) / max(dom[1], 1), 2),
+                                                      "note": "raw FETCH_SIZE / WRITE_SIZE x 1024 B (no x2: the K1 accesses are 16-byte pieces of 64 different member streams per "
+                                                              "instruction, between the guide's narrow and wide regimes)"}
+                if "roofline_scan" in out:
+                    keys = [k for k in per if k[0] in ("walk_scan_kernel", "scan_kernel", "index_count_kernel", "index_write_kernel", "index_guess_kernel")]
+                    if keys:
+                        tot = sum(per[k] for k in keys) * n_rec
+                        out["roofline_scan"]["traffic"] = int(tot)
+                        out["roofline_scan"]["traffic_note"] = ("raw FETCH_SIZE + WRITE_SIZE of the K2 / scan kernels per record (profiles/r06_hbm_traffic_pmc.txt) x the records of the step; the "
+                                                                "kernels gather one or two 128-byte lines per record, so the guide's x2 for wide streams does not apply")
+            except OSError:
+                pass
+        if args.full and world == 1 and not args.no_cpu_baseline and tool == "mappingqc":
             import oracle_lib as O
             sample = min(args.cpu_sample_reads if not args.ont else 150_000, n_rec)
             c_cpu, st, secs = O.baseline_wgs_stream(image, omim, 1, sample, sites=sites_arr, site_params=(1, 13, bool(args.ont)))
@@ -715,7 +764,7 @@ def main():
                                                                   "covered by the parity tests")
                 except Exception as e:   # never let the extra leg break the bench line
                     out["cpu_baseline_all_cores"] = {"error": str(e)[:200]}
-        elif world == 1 and not args.no_cpu_baseline:
+        elif args.full and world == 1 and not args.no_cpu_baseline:
             # coverage tools: the oracle's restatement (1 thread) on the first records of the same BAM, and the same sample through the GPU path as parity check
             import oracle_lib as O
             samp = prefix_image(image, min(int(image.size), args.cpu_sample_reads * BYTES_PER_READ_COMPRESSED))
@@ -740,7 +789,7 @@ def main():
                                    "counters_match_note": "per-line depth sums (BedCoverage) / per-base depth of the whole exome BED (BedLowCoverage) of the sample, GPU vs oracle, bit-exact"}
     # ---- the other named configs of BASELINE.json in the SAME line: configs[2] = BedCoverage / BedLowCoverage over the resident 30x image,
     # configs[4] = the ONT shard (behind the headline handle: it needs the HBM) ----
-    want_extra = rank == 0 and world == 1 and tool == "mappingqc" and not args.ont and not args.single_bam and os.environ.get("NGSQC_BENCH_NO_TOOLS") is None
+    want_extra = args.full and rank == 0 and world == 1 and tool == "mappingqc" and not args.ont and not args.single_bam and os.environ.get("NGSQC_BENCH_NO_TOOLS") is None
     if want_extra:
         import oracle_lib as O
         out["tools"] = {}
@@ -750,7 +799,8 @@ def main():
                 out["tools"][tag] = leg
             except Exception as e:   # never let an extra leg break the bench line
                 out["tools"][tl + (f"_baseq{bq}" if bq else "")] = {"error": str(e)[:300]}
-    mark("stage / roofline / cpu-baseline / tool legs done")
+    if args.full:
+        mark("stage / roofline / cpu-baseline / tool legs done")
     n_members_file = int(h.n_blocks) if not args.single_bam else None
     h.close()
     if want_extra and os.environ.get("NGSQC_BENCH_NO_ONT") is None:
@@ -763,7 +813,7 @@ def main():
             out["flavors"] = {"flavor5_refseq_40level_qual": flavor_leg(ngsqc, G, H, O, args, local_rank, 3)}
         except Exception as e:
             out["flavors"] = {"error": str(e)[:300]}
-    if args.single_bam and rank == 0 and tool == "mappingqc" and image is not None:
+    if args.full and args.single_bam and rank == 0 and tool == "mappingqc" and image is not None:
         # parity of the sharded path: the unsharded job on this rank's GPU over the whole BAM (all 1032 counters and the depth histogram)
         try:
             hf = ngsqc.Handle(data=image, device=local_rank)
@@ -780,10 +830,10 @@ def main():
     # ---- the other way to use N GPUs, in the same line: ONE BAM sharded over the ranks by BGZF member range (configs[1] at N GPUs; `value` above is
     # configs[3], one BAM per GPU). Fused shard job per rank, all-gather of the summaries, SUM all-reduce of counters / site counts / difference array. ----
     strong = None
-    if per_rank_seed and rank == 0:
+    if args.full and per_rank_seed and rank == 0:
         strong = {"skipped": "every rank holds a different BAM in this run (one BAM per GPU, seed + rank): the one-BAM-over-N-GPUs leg needs the same image on every rank - "
                              "run `bench.py --gpus N --single-bam`, or set NGSQC_BENCH_SHARED_IMAGE=1"}
-    if tool == "mappingqc" and not args.ont and not args.single_bam and image is not None and not per_rank_seed and os.environ.get("NGSQC_BENCH_NO_STRONG") is None:
+    if args.full and tool == "mappingqc" and not args.ont and not args.single_bam and image is not None and not per_rank_seed and os.environ.get("NGSQC_BENCH_NO_STRONG") is None:
         try:
             hs = ngsqc.Handle(data=image, device=local_rank, shard=(rank, world))
             k2 = max(1, min(args.steps, 5))
@@ -822,7 +872,7 @@ def main():
         if strong is not None:
             out["single_bam"] = strong
         # ---- end to end from a file: ngsqc_open(path) copies the image in the background while the first job already runs; and the tool itself ----
-        if world == 1 and tool == "mappingqc" and not args.ont and os.environ.get("NGSQC_BENCH_NO_E2E") is None:
+        if args.full and world == 1 and tool == "mappingqc" and not args.ont and os.environ.get("NGSQC_BENCH_NO_E2E") is None:
             try:
                 import shutil
                 # (a copy in /dev/shm is host memory: only when there is room for it next to the image itself)

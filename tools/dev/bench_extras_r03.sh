@@ -3,13 +3,13 @@
 O=gpurun_out/r3_extras; mkdir -p $O
 export NGSQC_BENCH_NO_STRONG=1 NGSQC_BENCH_NO_E2E=1
 C=/dev/shm/ngsqc_extras_f0.bam
-python bench.py --reads 96000000 --steps 3 --warmup 1 --tool bedcoverage --image-cache $C > $O/bedcoverage.json 2> $O/bedcoverage.err
-python bench.py --reads 96000000 --steps 3 --warmup 1 --tool bedlowcoverage --image-cache $C > $O/bedlowcoverage.json 2> $O/bedlowcoverage.err
-python bench.py --reads 96000000 --steps 3 --warmup 1 --tool bedlowcoverage --min-baseq 20 --image-cache $C > $O/bedlowcoverage_bq20.json 2> $O/bedlowcoverage_bq20.err
+python bench.py --full --reads 96000000 --steps 3 --warmup 1 --tool bedcoverage --image-cache $C > $O/bedcoverage.json 2> $O/bedcoverage.err
+python bench.py --full --reads 96000000 --steps 3 --warmup 1 --tool bedlowcoverage --image-cache $C > $O/bedlowcoverage.json 2> $O/bedlowcoverage.err
+python bench.py --full --reads 96000000 --steps 3 --warmup 1 --tool bedlowcoverage --min-baseq 20 --image-cache $C > $O/bedlowcoverage_bq20.json 2> $O/bedlowcoverage_bq20.err
 rm -f $C
-python bench.py --reads 96000000 --steps 3 --warmup 1 --flavor 3 > $O/mappingqc_flavor3.json 2> $O/mappingqc_flavor3.err
-python bench.py --reads 96000000 --steps 3 --warmup 1 --flavor 5 > $O/mappingqc_flavor5.json 2> $O/mappingqc_flavor5.err
-python bench.py --ont --steps 3 --warmup 1 > $O/ont.json 2> $O/ont.err
+python bench.py --full --reads 96000000 --steps 3 --warmup 1 --flavor 3 > $O/mappingqc_flavor3.json 2> $O/mappingqc_flavor3.err
+python bench.py --full --reads 96000000 --steps 3 --warmup 1 --flavor 5 > $O/mappingqc_flavor5.json 2> $O/mappingqc_flavor5.err
+python bench.py --full --ont --steps 3 --warmup 1 > $O/ont.json 2> $O/ont.err
 python tools/dev/job_probe.py 96000000 5 default,slots3,default,slots3 > $O/job_probe.log 2>&1
 for f in $O/*.json; do echo "== $f"; python - "$f" <<'PY'
 import json, sys

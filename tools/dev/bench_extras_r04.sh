@@ -4,11 +4,11 @@ O=gpurun_out/r4_extras; mkdir -p $O
 tools/dev/profile_r04.sh > $O/profile.log 2>&1; cp profiles/r04_* $O/ 2>/dev/null
 export NGSQC_BENCH_NO_STRONG=1 NGSQC_BENCH_NO_E2E=1
 C=/dev/shm/ngsqc_extras_f0.bam
-timeout 200 python bench.py --reads 96000000 --steps 3 --warmup 1 --tool bedcoverage --image-cache $C > $O/bedcoverage.json 2> $O/bedcoverage.err
-timeout 200 python bench.py --reads 96000000 --steps 3 --warmup 1 --tool bedlowcoverage --image-cache $C > $O/bedlowcoverage.json 2> $O/bedlowcoverage.err
+timeout 200 python bench.py --full --reads 96000000 --steps 3 --warmup 1 --tool bedcoverage --image-cache $C > $O/bedcoverage.json 2> $O/bedcoverage.err
+timeout 200 python bench.py --full --reads 96000000 --steps 3 --warmup 1 --tool bedlowcoverage --image-cache $C > $O/bedlowcoverage.json 2> $O/bedlowcoverage.err
 rm -f $C
-timeout 200 python bench.py --reads 96000000 --steps 3 --warmup 1 --flavor 3 --no-cpu-baseline > $O/mappingqc_flavor3.json 2> $O/mappingqc_flavor3.err
-timeout 300 python bench.py --ont --steps 3 --warmup 1 > $O/ont.json 2> $O/ont.err
+timeout 200 python bench.py --full --reads 96000000 --steps 3 --warmup 1 --flavor 3 --no-cpu-baseline > $O/mappingqc_flavor3.json 2> $O/mappingqc_flavor3.err
+timeout 300 python bench.py --full --ont --steps 3 --warmup 1 > $O/ont.json 2> $O/ont.err
 for f in $O/*.json; do echo "== $f"; python - "$f" <<'PY'
 import json, sys
 try:

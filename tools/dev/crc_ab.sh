@@ -5,7 +5,7 @@
 set -u
 R=${GRAFT_REPO_ROOT:-$(pwd)}; O=$R/gpurun_out; mkdir -p $O
 export NGSQC_BENCH_NO_STRONG=1 NGSQC_BENCH_NO_E2E=1 NGSQC_BENCH_NO_TOOLS=1 NGSQC_BENCH_NO_ONT=1
-CMD="python $R/bench.py --reads 48000000 --steps 6 --warmup 2 --no-cpu-baseline --image-cache /dev/shm/ngsqc_ab_48m.bam"
+CMD="python $R/bench.py --full --reads 48000000 --steps 6 --warmup 2 --no-cpu-baseline --image-cache /dev/shm/ngsqc_ab_48m.bam"
 cd /tmp && export TMPDIR=/tmp
 $CMD > /dev/null 2>&1   # (generates the image, pages the python stack in)
 : > $O/crc_ab.txt

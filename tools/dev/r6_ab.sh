@@ -4,7 +4,7 @@ set -u
 R=${GRAFT_REPO_ROOT:-$(pwd)}; O=$R/gpurun_out/${1:-ab}; mkdir -p $O; shift; TAGS="$@"
 export NGSQC_BENCH_NO_STRONG=1 NGSQC_BENCH_NO_E2E=1 NGSQC_BENCH_NO_TOOLS=1 NGSQC_BENCH_NO_ONT=1 NGSQC_BENCH_NO_FLAVORS=1
 cd /tmp && export TMPDIR=/tmp
-CMD="python $R/bench.py --steps 5 --warmup 1 --no-cpu-baseline --image-cache /tmp/ngsqc_ab_full.bam"
+CMD="python $R/bench.py --full --reads 620000000 --steps 5 --warmup 1 --no-cpu-baseline --image-cache /tmp/ngsqc_ab_full.bam"
 $CMD > $O/a1.json 2> $O/a1.err
 cp $R/ngs-bits_amd/libngsqc_hip.so /tmp/lib_a.so; RUNS="a1"
 NGSQC_K1_CHUNK_WAVES=6 $CMD > $O/a1_cw6.json 2> $O/a1_cw6.err; RUNS="$RUNS a1_cw6"

@@ -4,7 +4,7 @@ set -u
 R=${GRAFT_REPO_ROOT:-$(pwd)}; O=$R/gpurun_out/${1:-env}; mkdir -p $O; shift
 export NGSQC_BENCH_NO_STRONG=1 NGSQC_BENCH_NO_E2E=1 NGSQC_BENCH_NO_TOOLS=1 NGSQC_BENCH_NO_ONT=1 NGSQC_BENCH_NO_FLAVORS=1
 cd /tmp && export TMPDIR=/tmp
-CMD="python $R/bench.py --steps 5 --warmup 1 --no-cpu-baseline --image-cache /tmp/ngsqc_env_full.bam"
+CMD="python $R/bench.py --full --reads 620000000 --steps 5 --warmup 1 --no-cpu-baseline --image-cache /tmp/ngsqc_env_full.bam"
 i=0
 for spec in "" "$@"; do
   i=$((i+1)); ( for kv in $(echo "$spec" | tr ',' ' '); do export "$kv"; done; $CMD > $O/r$i.json 2> $O/r$i.err )

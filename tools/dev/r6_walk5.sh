@@ -8,7 +8,7 @@ i=0
 for T in "bedcoverage" "bedlowcoverage --min-baseq 20"; do
   for S in "$@"; do
     i=$((i+1)); E=""; [ "$S" != "-" ] && E=$(echo $S | tr ',' ' ')
-    env $E python $R/bench.py --reads $N --tool $T --steps 4 --warmup 1 --no-cpu-baseline --image-cache /tmp/ngsqc_w5.bam > $O/r$i.json 2> $O/r$i.err
+    env $E python $R/bench.py --full --reads $N --tool $T --steps 4 --warmup 1 --no-cpu-baseline --image-cache /tmp/ngsqc_w5.bam > $O/r$i.json 2> $O/r$i.err
     python - <<PY
 import json
 try:

@@ -4,7 +4,7 @@
   rocprofv3 --pmc FETCH_SIZE        -d gpurun_out/r1_fetch -o f -- <cmd>      (separate passes, no trace domains)
   rocprofv3 --pmc WRITE_SIZE        -d gpurun_out/r1_write -o w -- <cmd>
   rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_ANY -d gpurun_out/r1_sq -o s -- <cmd>
-  <cmd> = python bench.py --steps 3 --warmup 1 --no-cpu-baseline
+  <cmd> = python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline
 """
 import os
 import sqlite3
@@ -22,8 +22,8 @@ try:
 except Exception:
     pass
 CMD = ("python bench.py --steps 3 --warmup 1 --no-cpu-baseline   (48M-read shard per step, 1x MI355X)" if PFX == "r1" else
-       "NGSQC_BENCH_NO_STRONG=1 NGSQC_BENCH_NO_E2E=1 python bench.py --reads 48000000 --steps 3 --warmup 1 --no-cpu-baseline   (48M-read shard; K1 chunks per job: 3 until round 5, 4 since round 6 (chunks of 5 waves per CU); 6 jobs per run: 1 warm-up + 3 timed + the un-pipelined and the isolated-K1 extra steps; 1x MI355X; counter passes with NGSQC_K1_SERIAL=1 NGSQC_PIPELINE=0: every kernel alone on the chip)" if PFX in ("r3", "r4", "r5", "r6") else
-       "python bench.py --reads 48000000 --steps 3 --warmup 1 --no-cpu-baseline   (48M-read shard = 2 tiles per step, 1x MI355X; counter passes with NGSQC_K1_SERIAL=1 NGSQC_PIPELINE=0: every kernel alone on the chip)")
+       "NGSQC_BENCH_NO_STRONG=1 NGSQC_BENCH_NO_E2E=1 python bench.py --full --reads 48000000 --steps 3 --warmup 1 --no-cpu-baseline   (48M-read shard; K1 chunks per job: 3 until round 5, 4 since round 6 (chunks of 5 waves per CU); 6 jobs per run: 1 warm-up + 3 timed + the un-pipelined and the isolated-K1 extra steps; 1x MI355X; counter passes with NGSQC_K1_SERIAL=1 NGSQC_PIPELINE=0: every kernel alone on the chip)" if PFX in ("r3", "r4", "r5", "r6") else
+       "python bench.py --full --reads 48000000 --steps 3 --warmup 1 --no-cpu-baseline   (48M-read shard = 2 tiles per step, 1x MI355X; counter passes with NGSQC_K1_SERIAL=1 NGSQC_PIPELINE=0: every kernel alone on the chip)")
 out = open(f"profiles/{tag}_kernel_stats.txt", "w")
 c = sqlite3.connect(f"gpurun_out/{PFX}_trace/t_results.db")
 out.write(f"# rocprofv3 --kernel-trace --stats -- {CMD}\n")
