@@ -146,6 +146,40 @@ int ngsqc_lowhigh_runs(ngsqc_handle* h, const ngsqc_region* lines, int64_t n_lin
 int ngsqc_site_pileup(ngsqc_handle* h, const ngsqc_region* sites, int64_t n_sites, int32_t min_mapq, int32_t min_baseq,
                       int32_t include_not_properly_paired, int64_t* counts);
 
+/* ---- indel windows: BamReader::getIndels (src/cppNGS/BamReader.cpp:948-1125, count_fragments = false) for a table of windows, the indel half of
+ * BamReader::getVariantDetails (:888-946). A window is [start, end] (1-based, closed) as getIndels receives it (indelRegion widened by one base on each side),
+ * sorted by tid then start, each tid contiguous; windows may overlap. Its query allele: kind NGSQC_ALLELE_INS with the len inserted bases in allele,
+ * NGSQC_ALLELE_DEL with the len deleted reference bases in allele and the reference slice [start, end + len) in ref_slice (end - start + len bytes, upper
+ * case as FastaFileIndex::seq returns it, 0 behind the contig end), or NGSQC_ALLELE_NONE (n_match stays 0). counts[NGSQC_INDEL_NCOUNTERS * i + k]: */
+#define NGSQC_ALLELE_NONE 0
+#define NGSQC_ALLELE_INS  1
+#define NGSQC_ALLELE_DEL  2
+typedef struct ngsqc_indel_window {
+	int32_t tid, start, end;
+	int32_t kind, len;
+	const char* allele;      /* len bases */
+	const char* ref_slice;   /* NGSQC_ALLELE_DEL: end - start + len bases, else NULL */
+} ngsqc_indel_window;
+#define NGSQC_W_READS_MAPPED 0   /* reads overlapping the window that pass the filters (duplicate, proper pair unless include_npp, secondary / supplementary, unmapped) */
+#define NGSQC_W_READS_MAPQ0  1   /* ... of which MAPQ 0 (not counted further) */
+#define NGSQC_W_DEPTH        2   /* reads with start <= window.start and end >= window.end, minus one per N operation spanning the window */
+#define NGSQC_W_INS          3   /* I operations of those reads at a genome position in [start, end], one per operation */
+#define NGSQC_W_DEL          4   /* D operations ... */
+#define NGSQC_W_MATCH        5   /* ... equal to the query allele: "+SEQ" / "-REF" */
+#define NGSQC_INDEL_NCOUNTERS 6
+/* A read that the reference would walk (it spans the window and holds an I, D or N operation) and that holds an operation the reference throws on gives
+ * NGSQC_E_FORMAT "Unknown CIGAR operation". */
+int ngsqc_indel_windows(ngsqc_handle* h, const ngsqc_indel_window* windows, int64_t n_windows, int32_t include_not_properly_paired, int64_t* counts);
+/* getVariantDetails for a VCF: the site pileup of the SNVs (sites and site_counts as in ngsqc_site_pileup, with site_min_mapq / site_min_baseq; the
+ * reference asks getPileup for 1 / 13) and the indel windows in ONE decode of the file. count_fragments != 0: NGSQC_E_UNSUPPORTED. */
+typedef struct ngsqc_variant_params {
+	int32_t include_not_properly_paired;
+	int32_t count_fragments;
+	int32_t site_min_mapq, site_min_baseq;
+} ngsqc_variant_params;
+int ngsqc_variant_details(ngsqc_handle* h, const ngsqc_region* sites, int64_t n_sites, const ngsqc_indel_window* windows, int64_t n_windows,
+                          const ngsqc_variant_params* p, int64_t* site_counts, int64_t* window_counts);
+
 /* ---- raw-read QC pass: StatisticsReads::update(const BamAlignment&) (src/cppNGS/StatisticsReads.cpp:83-158), the loop
  * of `MappingQC -read_qc` (src/MappingQC/main.cpp:83-98). Secondary / supplementary records are skipped; single_end
  * counts every read as forward (otherwise read1 = forward). The reference throws on bases other than A/C/G/T/N and on
@@ -354,7 +388,7 @@ typedef struct ngsqc_timings {
 	int64_t n_tiles;                  /* tiles of the handle's member table */
 	int64_t members_inflated;         /* BGZF members that went through K1 during the last job (== members of the tiles visited) */
 	double depth_scan_ms;             /* the extra depth scan of a job */
-	double pileup_ms, reads_ms;       /* site pileup / raw-read QC consumers */
+	double pileup_ms, reads_ms;       /* site pileup (+ the indel windows of ngsqc_indel_windows / ngsqc_variant_details) / raw-read QC consumers */
 	double job_wall_ms;               /* host wall time of the last ngsqc_run_job (setup, all tiles, result copies) */
 	int64_t members_second_chance;    /* members whose launch ran out of token pages and that were inflated again with the worst-case pool (since the handle was opened) */
 	int64_t members_third_chance;     /* ... and again with the bound that holds for every valid member (members of thousands of DEFLATE blocks) */

@@ -64,6 +64,19 @@ class JobDesc(C.Structure):
                 ("read_qc", C.c_int32), ("read_qc_single_end", C.c_int32), ("reserved", C.c_int32)]
 
 
+class IndelWindow(C.Structure):
+    _fields_ = [("tid", C.c_int32), ("start", C.c_int32), ("end", C.c_int32), ("kind", C.c_int32), ("len", C.c_int32),
+                ("allele", C.c_char_p), ("ref_slice", C.c_char_p)]
+
+
+class VariantParams(C.Structure):
+    _fields_ = [("include_not_properly_paired", C.c_int32), ("count_fragments", C.c_int32), ("site_min_mapq", C.c_int32), ("site_min_baseq", C.c_int32)]
+
+
+ALLELE_NONE, ALLELE_INS, ALLELE_DEL = 0, 1, 2
+INDEL_COUNTER_NAMES = ("reads_mapped", "reads_mapq0", "depth", "n_ins", "n_del", "n_match")   # NGSQC_W_* order
+
+
 class JobResult(C.Structure):
     _fields_ = [("counters", C.c_void_p), ("gc_reads", C.c_void_p), ("site_counts", C.c_void_p), ("read_stats", C.c_void_p)]
 
@@ -136,6 +149,8 @@ def lib():
         L.ngsqc_get_timings_sized.restype = i32; L.ngsqc_get_timings_sized.argtypes = [vp, vp, C.c_size_t]; L.ngsqc_abi_version.restype = i32
         L.ngsqc_version.restype = cp; L.ngsqc_device_count.restype = i32; L.ngsqc_device_count.argtypes = []
         L.ngsqc_site_pileup.restype = i32; L.ngsqc_site_pileup.argtypes = [vp, vp, i64, C.c_int32, C.c_int32, C.c_int32, vp]
+        L.ngsqc_indel_windows.restype = i32; L.ngsqc_indel_windows.argtypes = [vp, vp, i64, C.c_int32, vp]
+        L.ngsqc_variant_details.restype = i32; L.ngsqc_variant_details.argtypes = [vp, vp, i64, vp, i64, C.POINTER(VariantParams), vp, vp]
         L.ngsqc_scan_reads.restype = i32; L.ngsqc_scan_reads.argtypes = [vp, C.c_int32, C.POINTER(ReadStats)]
         L.ngsqc_read_length_hist.restype = i32; L.ngsqc_read_length_hist.argtypes = [vp, vp, i64]
         L.ngsqc_read_cycle_stats.restype = i32; L.ngsqc_read_cycle_stats.argtypes = [vp, vp, i64]
@@ -180,7 +195,7 @@ EXPORTS = [
     "ngsqc_depth_device", "ngsqc_depth_diff_copy", "ngsqc_depth_diff_set", "ngsqc_depth_finalize",
     "ngsqc_run_job", "ngsqc_depth_select", "ngsqc_depth_reduce", "ngsqc_region_read_counts", "ngsqc_upload_wait", "ngsqc_run_job_partial", "ngsqc_bai_range", "ngsqc_open_range", "ngsqc_header_text", "ngsqc_open_regions", "ngsqc_open_head",
     "ngsqc_write_bai", "ngsqc_bai_assemble", "ngsqc_bgzf_scan", "ngsqc_write_csi", "ngsqc_csi_assemble", "ngsqc_bai_ranges",
-    "ngsqc_set_reference", "ngsqc_set_cram_skip", "ngsqc_set_cram_skip_thread", "ngsqc_cram_to_bam",
+    "ngsqc_set_reference", "ngsqc_set_cram_skip", "ngsqc_set_cram_skip_thread", "ngsqc_cram_to_bam", "ngsqc_indel_windows", "ngsqc_variant_details",
 ]
 
 
@@ -313,6 +328,25 @@ def _regions_array(regions):
     for i, (tid, s, e) in enumerate(regions):
         arr[i].tid, arr[i].start, arr[i].end = int(tid), int(s), int(e)
     return arr
+
+
+def _bytes(x):
+    return x.encode("ascii") if isinstance(x, str) else bytes(x)
+
+
+def _windows_array(windows):
+    """windows: (tid, start, end, kind, allele, ref_slice) rows (allele / ref_slice: str or bytes; ref_slice only for ALLELE_DEL). Returns the C array and the
+    byte strings it points into (kept alive by the caller for the call)."""
+    arr = (IndelWindow * max(len(windows), 1))(); keep = []
+    for i, (tid, s, e, kind, allele, ref_slice) in enumerate(windows):
+        a = _bytes(allele or b""); keep.append(a)
+        w = arr[i]; w.tid, w.start, w.end, w.kind, w.len, w.allele = int(tid), int(s), int(e), int(kind), len(a), a
+        if kind == ALLELE_DEL:
+            r = _bytes(ref_slice); keep.append(r)
+            if len(r) != int(e) - int(s) + len(a):
+                raise ValueError("the reference slice of a deletion window covers [start, end + len)")
+            w.ref_slice = r
+    return arr, keep
 
 
 class Handle:
@@ -487,6 +521,26 @@ class Handle:
         out = np.zeros((max(n, 1), 8), dtype=np.int64)
         self._chk(lib().ngsqc_site_pileup(self.h, ptr, n, min_mapq, min_baseq, int(include_not_properly_paired), out.ctypes.data))
         return out[:n]
+
+    def indel_windows(self, windows, include_not_properly_paired=False):
+        """BamReader::getIndels for a table of windows: (tid, start, end, kind, allele, ref_slice) rows sorted by tid then start (see _windows_array).
+        Returns int64[n, 6] in INDEL_COUNTER_NAMES order."""
+        arr, keep = _windows_array(windows); n = len(windows)
+        out = np.zeros((max(n, 1), 6), dtype=np.int64)
+        self._chk(lib().ngsqc_indel_windows(self.h, C.cast(arr, C.c_void_p), n, int(include_not_properly_paired), out.ctypes.data))
+        del keep
+        return out[:n]
+
+    def variant_details(self, sites, windows, include_not_properly_paired=False, count_fragments=False, site_min_mapq=1, site_min_baseq=13):
+        """BamReader::getVariantDetails for a VCF in one decode: the site pileup of the SNV sites ((tid, pos) sorted, as site_pileup; the reference asks
+        getPileup for MAPQ >= 1 and base quality >= 13) and the indel windows (as indel_windows). Returns (int64[n_sites, 8], int64[n_windows, 6])."""
+        sarr = _regions_array([(t, p, p) for t, p in sites]); ns = len(sites)
+        warr, keep = _windows_array(windows); nw = len(windows)
+        prm = VariantParams(int(include_not_properly_paired), int(count_fragments), int(site_min_mapq), int(site_min_baseq))
+        sc = np.zeros((max(ns, 1), 8), dtype=np.int64); wc = np.zeros((max(nw, 1), 6), dtype=np.int64)
+        self._chk(lib().ngsqc_variant_details(self.h, C.cast(sarr, C.c_void_p), ns, C.cast(warr, C.c_void_p), nw, C.byref(prm), sc.ctypes.data, wc.ctypes.data))
+        del keep
+        return sc[:ns], wc[:nw]
 
     # ---- one BAM sharded over several handles (include/ngsqc.h, "sharded" section) ----
     def scan_mapping_partial(self, mode, **kw):

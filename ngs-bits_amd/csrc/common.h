@@ -172,6 +172,18 @@ void launch_pileup(const uint8_t* infl, const int64_t* recoff, int64_t n_rec, in
 void launch_pileup_long(const uint8_t* infl, const int64_t* recoff, const int64_t* long_list, const unsigned long long* d_n_long /* count on the device */, int64_t n_long_max, const int32_t* site_pos, const int32_t* tid_last,
                         const int32_t* bucket, const int64_t* tid_bucket0, int min_baseq, uint32_t* counts, hipStream_t s);
 
+// indel windows (indel.hip: BamReader::getIndels for a table of windows; counts = u32[n_windows][8], see there). start: 1-based window starts, sorted per
+// reference; win: the rest of each window; pool: query alleles and reference slices; buckets as in the site pileup; tid_maxlen: longest window of a reference
+struct IndelWin { int32_t end, kind, len, pad; int64_t qoff, soff; };
+struct IndelTables
+{
+	const int32_t* start; const IndelWin* win; const uint8_t* pool;
+	const int32_t* tid_first; const int32_t* tid_last; const int32_t* tid_maxlen; const int32_t* bucket; const int64_t* tid_bucket0;
+	int32_t n_ref, include_npp;
+};
+void launch_indel(const uint8_t* infl, const int64_t* recoff, int64_t n_rec, const IndelTables& w, uint32_t* counts, int64_t* long_list, unsigned long long* long_count, hipStream_t s);
+void launch_indel_long(const uint8_t* infl, const int64_t* recoff, const int64_t* long_list, const unsigned long long* d_n_long, int64_t n_long_max, const IndelTables& w, uint32_t* counts, hipStream_t s);
+
 // ---- raw-read QC pass (reads.hip): StatisticsReads::update(BamAlignment) ----
 constexpr int RQ_PASSES = 5, RQ_CYC = RQ_PASSES * 64;   // per-cycle statistics are kept for the first 320 cycles (every Illumina read length)
 enum { RA_FWD, RA_REV, RA_BASES, RA_A, RA_C, RA_G, RA_T, RA_N, RA_BAD_BASE, RA_BAD_QUAL, RA_BQ0, RA_RQ0 = RA_BQ0 + 100, RA_QD0 = RA_RQ0 + 100, RA_TOTAL = RA_QD0 + 120 };

@@ -323,6 +323,81 @@ struct PileupState
 	}
 };
 
+// indel windows of a table of variants (BamReader::getIndels per indel variant in the reference; indel.hip). Counts stay u32 on the device for the whole job:
+// a window sees at most one count per record of the file
+struct IndelState
+{
+	DevBuf<int32_t> d_start, d_tf, d_tl, d_maxlen, d_bucket; DevBuf<int64_t> d_tb0; DevBuf<IndelWin> d_win; DevBuf<uint8_t> d_pool; DevBuf<uint32_t> d_cnt; DevBuf<unsigned long long> d_nlong;
+	IndelTables t{}; int64_t n = 0; double stage_ms = 0;
+	void begin(ngsqc_handle* h, const ngsqc_indel_window* w, int64_t nw, int32_t npp)
+	{
+		n = nw; stage_ms = 0;
+		const int n_ref = (int)h->ref_names.size();
+		std::vector<int32_t> start((size_t)n), tf((size_t)std::max(n_ref, 1), 0), tl((size_t)std::max(n_ref, 1), 0), maxlen((size_t)std::max(n_ref, 1), 1);
+		std::vector<IndelWin> win((size_t)n); std::vector<uint8_t> pool;
+		std::vector<uint8_t> seen((size_t)std::max(n_ref, 1), 0);
+		for (int64_t i = 0; i < n; ++i)
+		{
+			const ngsqc_indel_window& x = w[i];
+			if (x.tid < 0 || x.tid >= n_ref) throw ArgError("window with invalid reference id");
+			if (x.start < 1 || x.end < x.start) throw ArgError("invalid window range");
+			if (x.kind < NGSQC_ALLELE_NONE || x.kind > NGSQC_ALLELE_DEL || x.len < 0 || (x.kind != NGSQC_ALLELE_NONE && x.len > 0 && !x.allele)) throw ArgError("invalid window allele");
+			if (x.kind == NGSQC_ALLELE_DEL && x.len > 0 && !x.ref_slice) throw ArgError("a deletion window needs its reference slice");
+			if (i > 0 && w[i - 1].tid == x.tid) { if (w[i - 1].start > x.start) throw ArgError("windows must be sorted by start within a reference"); }
+			else { if (seen[(size_t)x.tid]) throw ArgError("windows of one reference must be contiguous"); seen[(size_t)x.tid] = 1; tf[(size_t)x.tid] = (int32_t)i; }
+			tl[(size_t)x.tid] = (int32_t)i + 1; start[(size_t)i] = x.start;
+			maxlen[(size_t)x.tid] = std::max(maxlen[(size_t)x.tid], x.end - x.start + 1);
+			IndelWin& d = win[(size_t)i]; d.end = x.end; d.kind = x.kind; d.len = x.kind == NGSQC_ALLELE_NONE ? 0 : x.len; d.pad = 0; d.qoff = (int64_t)pool.size(); d.soff = d.qoff;
+			if (d.len > 0) pool.insert(pool.end(), (const uint8_t*)x.allele, (const uint8_t*)x.allele + d.len);
+			if (x.kind == NGSQC_ALLELE_DEL && d.len > 0) { d.soff = (int64_t)pool.size(); pool.insert(pool.end(), (const uint8_t*)x.ref_slice, (const uint8_t*)x.ref_slice + (x.end - x.start + d.len)); }
+		}
+		if (pool.empty()) pool.push_back(0);
+		std::vector<int64_t> tb0((size_t)n_ref + 1, 0); std::vector<int32_t> bucket;   // 64 kb buckets as in the site pileup: bucket -> first window starting at or behind it
+		for (int r = 0; r < n_ref; ++r)
+		{
+			tb0[(size_t)r] = (int64_t)bucket.size();
+			if (tf[(size_t)r] >= tl[(size_t)r]) continue;
+			const int64_t nb = (std::max<int64_t>(h->ref_lens[(size_t)r], start[(size_t)tl[(size_t)r] - 1]) >> PILEUP_BUCKET_SHIFT) + 2;
+			int32_t i = tf[(size_t)r];
+			for (int64_t b = 0; b < nb; ++b) { const int64_t lo = b << PILEUP_BUCKET_SHIFT; while (i < tl[(size_t)r] && start[(size_t)i] < lo) ++i; bucket.push_back(i); }
+		}
+		tb0[(size_t)n_ref] = (int64_t)bucket.size();
+		if (bucket.empty()) bucket.push_back(0);
+		d_start.upload(start, h->stream); d_win.upload(win, h->stream); d_pool.upload(pool, h->stream); d_tf.upload(tf, h->stream); d_tl.upload(tl, h->stream);
+		d_maxlen.upload(maxlen, h->stream); d_bucket.upload(bucket, h->stream); d_tb0.upload(tb0, h->stream);
+		d_cnt.ensure((size_t)n * 8); d_nlong.ensure(1);
+		HIPCHK(hipMemsetAsync(d_cnt.p, 0, (size_t)n * 8 * sizeof(uint32_t), h->stream));
+		HIPCHK(hipStreamSynchronize(h->stream));   // (the staging vectors go out of scope)
+		t.start = d_start.p; t.win = d_win.p; t.pool = d_pool.p; t.tid_first = d_tf.p; t.tid_last = d_tl.p; t.tid_maxlen = d_maxlen.p; t.bucket = d_bucket.p; t.tid_bucket0 = d_tb0.p;
+		t.n_ref = n_ref; t.include_npp = npp ? 1 : 0;
+	}
+	void tile(ngsqc_handle* h, const TileCtx& c)
+	{
+		if (n == 0) return;
+		const size_t iv = h->evlog->begin(h->stream, &stage_ms);
+		const int64_t* offs = ensure_recoff(h);
+		h->d_long.ensure_slack((size_t)std::max<int64_t>(c.n_rec, 1));
+		HIPCHK(hipMemsetAsync(d_nlong.p, 0, sizeof(unsigned long long), h->stream));
+		launch_indel(c.infl, offs, c.n_rec, t, d_cnt.p, h->d_long.p, d_nlong.p, h->stream);
+		launch_indel_long(c.infl, offs, h->d_long.p, d_nlong.p, c.n_rec, t, d_cnt.p, h->stream);   // (the count of long records stays on the device)
+		h->evlog->end(iv, h->stream);
+	}
+	void end(ngsqc_handle* h, int64_t* counts)
+	{
+		if (n == 0) return;
+		std::vector<uint32_t> out((size_t)n * 8);
+		HIPCHK(hipMemcpyAsync(out.data(), d_cnt.p, out.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+		HIPCHK(hipStreamSynchronize(h->stream));
+		for (int64_t i = 0; i < n; ++i)
+		{
+			const uint32_t* o = out.data() + 8 * i; int64_t* d = counts + NGSQC_INDEL_NCOUNTERS * i;
+			if (o[6]) throw FormatError("Unknown CIGAR operation in a read of window " + std::to_string(i) + "!");
+			d[NGSQC_W_READS_MAPPED] = o[0]; d[NGSQC_W_READS_MAPQ0] = o[1]; d[NGSQC_W_DEPTH] = (int32_t)o[2];
+			d[NGSQC_W_INS] = o[3]; d[NGSQC_W_DEL] = o[4]; d[NGSQC_W_MATCH] = o[5];
+		}
+	}
+};
+
 // raw-read QC (StatisticsReads::update). The read-length histogram grows with the longest read seen so far.
 struct ReadsState
 {
@@ -571,11 +646,16 @@ void depth_setup(ngsqc_handle* h, const ngsqc_depth_params* p, DepthSet& D, Scan
 }
 
 // The fused job: every requested consumer sees every tile once.
-void run_job(ngsqc_handle* h, const ngsqc_job_desc* j, ngsqc_job_result* r, ngsqc_shard_summary* shard_out = nullptr)
+// indel windows of ngsqc_variant_details / ngsqc_indel_windows: a consumer the public job struct does not name
+struct IndelJob { const ngsqc_indel_window* windows; int64_t n; int32_t include_npp; int64_t* counts; };
+
+void run_job(ngsqc_handle* h, const ngsqc_job_desc* j, ngsqc_job_result* r, ngsqc_shard_summary* shard_out = nullptr, const IndelJob* ij = nullptr)
 {
 	if (!j || !r) throw ArgError("null argument");
 	const bool part = shard_out != nullptr;   // a shard: additive results only (mapping: summary now, counters from ngsqc_scan_mapping_finish; depth: the un-prefixed difference arrays)
 	const bool do_map = j->mapping != nullptr, do_depth = j->depth != nullptr, do_sites = j->n_sites > 0, do_reads = j->read_qc != 0;
+	const bool do_indel = ij && ij->n > 0;
+	if (do_indel && (part || !ij->windows || !ij->counts)) throw ArgError("indel window job without windows / count buffer");
 	if (do_map && !part && !r->counters) throw ArgError("mapping job without a counter buffer");
 	if (part && (!do_map || do_reads)) throw ArgError("a shard job needs the mapping scan and cannot run the raw-read QC");
 	if (do_sites && (!j->sites || !r->site_counts)) throw ArgError("site pileup job without sites / count buffer");
@@ -585,13 +665,14 @@ void run_job(ngsqc_handle* h, const ngsqc_job_desc* j, ngsqc_job_result* r, ngsq
 	dbg_stamp("job: start");
 	h->tm.scan_ms = 0; h->tm.scan_kernel_ms = 0; h->tm.scan_launches = 0; h->tm.finalize_ms = 0; h->tm.depth_scan_ms = 0; h->tm.pileup_ms = 0; h->tm.reads_ms = 0; h->tm.scan_algorithmic_bytes = 0;   // (every per-consumer field of the previous job)
 	Timer total(h->stream); total.start();
-	ngsqc_handle::Partial local_map; ScanState dscan; PileupState pile; ReadsState reads;
+	ngsqc_handle::Partial local_map; ScanState dscan; PileupState pile; IndelState indel; ReadsState reads;
 	if (part) { delete h->partial; h->partial = new ngsqc_handle::Partial(); }
 	ngsqc_handle::Partial& map = part ? *h->partial : local_map;
 	if (do_map) { mapping_setup(h, j->mapping, map); map.scan.in_pass_fix = !part; map.scan.begin(h); }
 	if (do_depth) { depth_setup(h, j->depth, h->ds[1], dscan); dscan.in_pass_fix = false; dscan.begin(h); }
 	if (do_sites) pile.begin(h, j->sites, j->n_sites, j->site_min_mapq, j->site_min_baseq, j->site_include_npp);
 	if (do_sites && do_map) pile.attach(map.scan.sp, &map.scan);   // (the pileup's candidates come from the scan that rides K2's chain walk)
+	if (do_indel) indel.begin(h, ij->windows, ij->n, ij->include_npp);
 	if (do_reads) reads.begin(h, j->read_qc_single_end);
 	const double w1 = wall_ms();
 	const bool depth_rides = do_depth && (j->depth->min_baseq <= 0 || !(getenv("NGSQC_BASEQ_RIDE") && atoi(getenv("NGSQC_BASEQ_RIDE")) == 0));
@@ -600,7 +681,7 @@ void run_job(ngsqc_handle* h, const ngsqc_job_desc* j, ngsqc_job_result* r, ngsq
 	// order-dependent fix-ups ask for them), the site pileup works on the walk's candidate list; the extra depth scan and the raw-read QC read every record
 	struct LazyGuard { ngsqc_handle* h; ~LazyGuard() { h->lazy_recoff = false; } } lg{h};
 	// (round 6: a coverage tool's job - the depth scan alone, riding the walk - does not expand them either: 0.23 ms per tile of the 30x file, 6 % of its scan stage)
-	h->lazy_recoff = !part && !do_reads && ((do_map && !do_depth) || (!do_map && depth_rides && !do_sites)) && !getenv("NGSQC_EAGER_RECOFF");
+	h->lazy_recoff = !part && !do_reads && !do_indel && ((do_map && !do_depth) || (!do_map && depth_rides && !do_sites)) && !getenv("NGSQC_EAGER_RECOFF");
 	stream_tiles(h, [&](const TileCtx& c) {
 		if (do_map) map.scan.tile(h, c);
 		if (part && c.ord_base == 0 && c.n_rec > 0)
@@ -612,6 +693,7 @@ void run_job(ngsqc_handle* h, const ngsqc_job_desc* j, ngsqc_job_result* r, ngsq
 		}
 		if (do_depth) dscan.tile(h, c);
 		if (do_sites) pile.tile(h, c);
+		if (do_indel) indel.tile(h, c);
 		if (do_reads) reads.tile(h, c);
 		return true;
 	});
@@ -647,6 +729,7 @@ void run_job(ngsqc_handle* h, const ngsqc_job_desc* j, ngsqc_job_result* r, ngsq
 		if (!do_map) { h->tm.scan_algorithmic_bytes = (int64_t)dscan.dev[A_ALG_BYTES]; h->tm.scan_kernel_ms = dscan.kernel_ms; h->tm.scan_launches = dscan.launches; h->tm.scan_ms = dscan.stage_ms; }
 	}
 	if (do_sites) { pile.end(h, r->site_counts); h->tm.pileup_ms = pile.stage_ms; }
+	if (do_indel) { indel.end(h, ij->counts); h->tm.pileup_ms += indel.stage_ms; }   // (the timings struct keeps its layout: the windows' stage is booked with the site pileup)
 	if (do_reads) { reads.end(h, r->read_stats); h->tm.reads_ms = reads.stage_ms; }
 	h->cur_ds = do_map || !do_depth ? 0 : 1;
 	h->tm.total_ms = total.stop();
@@ -843,6 +926,36 @@ int ngsqc_site_pileup(ngsqc_handle* h, const ngsqc_region* sites, int64_t n_site
 		ngsqc_job_result r{}; r.site_counts = counts;
 		const int keep = h->cur_ds;
 		run_job(h, &j, &r);
+		h->cur_ds = keep;
+	});
+}
+
+int ngsqc_indel_windows(ngsqc_handle* h, const ngsqc_indel_window* windows, int64_t n_windows, int32_t include_not_properly_paired, int64_t* counts)
+{
+	return guarded(h, [&] {
+		if (n_windows < 0 || (n_windows && (!windows || !counts))) throw ArgError("null argument");
+		if (n_windows == 0) return;
+		ngsqc_job_desc j{}; ngsqc_job_result r{};
+		const IndelJob ij{windows, n_windows, include_not_properly_paired, counts};
+		const int keep = h->cur_ds;
+		run_job(h, &j, &r, nullptr, &ij);
+		h->cur_ds = keep;
+	});
+}
+
+// BamReader::getVariantDetails for a table of variants: the SNVs' pileup and the indels' windows in one decode of the file
+int ngsqc_variant_details(ngsqc_handle* h, const ngsqc_region* sites, int64_t n_sites, const ngsqc_indel_window* windows, int64_t n_windows,
+                          const ngsqc_variant_params* p, int64_t* site_counts, int64_t* window_counts)
+{
+	return guarded(h, [&] {
+		if (!p || n_sites < 0 || n_windows < 0 || (n_sites && (!sites || !site_counts)) || (n_windows && (!windows || !window_counts))) throw ArgError("null argument");
+		if (p->count_fragments) throw std::domain_error("count_fragments is not supported by ngsqc_variant_details");
+		if (n_sites == 0 && n_windows == 0) return;
+		ngsqc_job_desc j{}; j.sites = sites; j.n_sites = n_sites; j.site_min_mapq = p->site_min_mapq; j.site_min_baseq = p->site_min_baseq; j.site_include_npp = p->include_not_properly_paired;
+		ngsqc_job_result r{}; r.site_counts = site_counts;
+		const IndelJob ij{windows, n_windows, p->include_not_properly_paired, window_counts};
+		const int keep = h->cur_ds;
+		run_job(h, &j, &r, nullptr, &ij);
 		h->cur_ds = keep;
 	});
 }

@@ -13,14 +13,13 @@
 // the reference increments the whole reference span [start,end] of a read (RegionDepth::incrementRegion,
 // Statistics.cpp:45-53), which is exactly a prefix sum over these differences. All arithmetic is integer.
 #include "common.h"
+#include "rec.h"
 #include <algorithm>
 #include <cstring>
 #include <rocprim/device/device_radix_sort.hpp>
 
 namespace ngsqc {
 
-__device__ __forceinline__ uint32_t ld32(const uint8_t* p) { uint32_t v; __builtin_memcpy(&v, p, 4); return v; }
-__device__ __forceinline__ uint16_t ld16(const uint8_t* p) { uint16_t v; __builtin_memcpy(&v, p, 2); return v; }
 // The refresh of a per-lane cache (region search, next known site) is a rare branch that leaves loaded values in registers; it waits for them ITSELF (round 6): a
 // load still pending at the join makes the compiler wait with vmcnt(0) at the values' first use behind the join - in the walk that is a wait for the next record's
 // prefetched header in EVERY trip, taken or not (worth about 1 % on the 30x walk: 2.72 against 2.75 ms per 48 M records, profiles/r06_kernel_stats_serial.txt).
@@ -42,68 +41,6 @@ struct Acc
 	int ns_tid = -2; bool ns_val = false;   // tid_nonspecial[ns_tid] (round 5: one dependent load per record less - a walker changes reference a few times per file)
 };
 
-struct RecView
-{
-	const uint8_t* core;   // points at refID (record + 4)
-	uint32_t bs; int32_t tid, pos; uint32_t l_name, mapq, n_cigar_raw, flag; int32_t l_seq, isize;
-	const uint8_t* cigar; uint32_t n_cigar;  // effective CIGAR (may be the CG tag payload)
-};
-
-// the fixed part of a record as the chain walk keeps it one record ahead: block_size, refID, pos, (l_read_name | mapq | bin), (n_cigar_op | flag), l_seq, tlen
-struct Hdr { uint32_t bs, tid, pos, w, w2, l_seq, isize; };
-__device__ __forceinline__ Hdr load_hdr(const uint8_t* p)
-{
-	Hdr h; uint32_t a[4], b[2];
-	__builtin_memcpy(a, p, 16); __builtin_memcpy(b, p + 16, 8);
-	h.bs = a[0]; h.tid = a[1]; h.pos = a[2]; h.w = a[3]; h.w2 = b[0]; h.l_seq = b[1]; h.isize = ld32(p + 32);
-	return h;
-}
-__device__ __forceinline__ RecView make_rec(const uint8_t* infl, int64_t off, const Hdr& h)
-{
-	RecView r; const uint8_t* p = infl + off;
-	r.bs = h.bs; r.core = p + 4; r.tid = (int32_t)h.tid; r.pos = (int32_t)h.pos;
-	r.l_name = h.w & 0xff; r.mapq = (h.w >> 8) & 0xff; r.n_cigar_raw = h.w2 & 0xffff; r.flag = h.w2 >> 16;
-	r.l_seq = (int32_t)h.l_seq; r.isize = (int32_t)h.isize;
-	r.cigar = p + 36 + r.l_name; r.n_cigar = r.n_cigar_raw;
-	return r;
-}
-__device__ __forceinline__ RecView load_rec(const uint8_t* infl, int64_t off)
-{
-	RecView r; const uint8_t* p = infl + off;
-	r.bs = ld32(p); r.core = p + 4;
-	r.tid = (int32_t)ld32(p + 4); r.pos = (int32_t)ld32(p + 8);
-	uint32_t w = ld32(p + 12), w2 = ld32(p + 16);
-	r.l_name = w & 0xff; r.mapq = (w >> 8) & 0xff; r.n_cigar_raw = w2 & 0xffff; r.flag = w2 >> 16;
-	r.l_seq = (int32_t)ld32(p + 20); r.isize = (int32_t)ld32(p + 32);
-	r.cigar = p + 36 + r.l_name; r.n_cigar = r.n_cigar_raw;
-	return r;
-}
-__device__ __forceinline__ const uint8_t* rec_qual(const RecView& r) { return r.core + 32 + r.l_name + 4ull * r.n_cigar_raw + ((uint32_t)r.l_seq + 1) / 2; }
-__device__ __forceinline__ const uint8_t* rec_aux(const RecView& r) { return rec_qual(r) + (uint32_t)r.l_seq; }
-__device__ __forceinline__ const uint8_t* rec_end(const RecView& r) { return r.core + r.bs; }
-
-// linear aux scan (what htslib's bam_aux_get does); returns pointer to the type byte or nullptr
-__device__ static const uint8_t* aux_find(const uint8_t* p, const uint8_t* end, uint8_t t0, uint8_t t1)
-{
-	while (p + 3 <= end)
-	{
-		const uint8_t* t = p + 2;
-		if (p[0] == t0 && p[1] == t1) return t;
-		uint8_t type = *t; const uint8_t* v = t + 1; size_t sz;
-		switch (type)
-		{
-			case 'A': case 'c': case 'C': sz = 1; break;
-			case 's': case 'S': sz = 2; break;
-			case 'i': case 'I': case 'f': sz = 4; break;
-			case 'd': sz = 8; break;
-			case 'Z': case 'H': { const uint8_t* q = v; while (q < end && *q) ++q; sz = (size_t)(q - v) + 1; break; }
-			case 'B': { if (v + 5 > end) return nullptr; uint8_t st = v[0]; uint32_t n = ld32(v + 1); size_t es = (st == 'c' || st == 'C') ? 1 : (st == 's' || st == 'S') ? 2 : 4; sz = 5 + es * (size_t)n; break; }
-			default: return nullptr;
-		}
-		p = v + sz;
-	}
-	return nullptr;
-}
 // BamAlignment::tagi (BamReader.cpp:286-297)
 __device__ static int aux_tagi(const RecView& r, uint8_t t0, uint8_t t1)
 {
@@ -420,12 +357,6 @@ __device__ static void classify(const ScanParams& p, const RecView& r, long long
 	if (dup) a.n[A_DUP]++;
 }
 
-__device__ __forceinline__ long long wave_sum(long long v)
-{
-	for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-	return v;
-}
-
 __device__ static void flush(const ScanParams& p, Acc& a, uint32_t* lds_hist)
 {
 	const int lane = threadIdx.x & 63;
@@ -631,8 +562,7 @@ __global__ __launch_bounds__(256) void scan_long_kernel(const ScanParams p, long
 					unsigned long long cg = 0; uint32_t n = 0;
 					if (lane == 0)
 					{
-						const uint8_t* t = aux_find(rec_aux(r), rec_end(r), 'C', 'G');
-						if (t && t[0] == 'B' && t[1] == 'I') { n = ld32(t + 2); if (n >= r.n_cigar_raw && n < (1u << 29)) cg = (unsigned long long)(uintptr_t)(t + 6); }
+						cg = (unsigned long long)(uintptr_t)rec_cg_tag(r, n);
 					}
 					cg = __shfl(cg, 0); n = __shfl(n, 0);
 					if (cg) { r.cigar = (const uint8_t*)(uintptr_t)cg; r.n_cigar = n; redo = true; }
@@ -1210,16 +1140,7 @@ __global__ __launch_bounds__(256) void pileup_kernel(const uint8_t* __restrict__
 		if (r.tid < 0 || r.tid >= n_ref) continue;
 		const int first = tid_first[r.tid], last = tid_last[r.tid];
 		if (first >= last) continue;
-		// CG:B,I long CIGAR (htslib bam_tag2cigar)
-		if (r.n_cigar_raw > 0 && r.pos >= 0)
-		{
-			const uint32_t c0 = ld32(r.cigar);
-			if ((c0 & 15u) == 4 && (int32_t)(c0 >> 4) == r.l_seq)
-			{
-				const uint8_t* t = aux_find(rec_aux(r), rec_end(r), 'C', 'G');
-				if (t && t[0] == 'B' && t[1] == 'I') { const uint32_t n = ld32(t + 2); if (n >= r.n_cigar_raw && n < (1u << 29)) { r.cigar = t + 6; r.n_cigar = n; } }
-			}
-		}
+		rec_apply_cg(r);   // CG:B,I long CIGAR
 		if (r.n_cigar > (uint32_t)LONG_CIGAR) { long_list[atomicAdd(long_count, 1ull)] = li; continue; }   // wave-per-record path (pileup_long_kernel)
 		long long ref_len = 0;
 		for (uint32_t k = 0; k < r.n_cigar; ++k) { const uint32_t c = ld32(r.cigar + 4ull * k); if ((0x18Du >> (c & 15u)) & 1u) ref_len += c >> 4; }
@@ -1265,8 +1186,7 @@ __global__ __launch_bounds__(256) void pileup_long_kernel(const uint8_t* __restr
 				unsigned long long cg = 0; uint32_t n = 0;
 				if (lane == 0)
 				{
-					const uint8_t* t = aux_find(rec_aux(r), rec_end(r), 'C', 'G');
-					if (t && t[0] == 'B' && t[1] == 'I') { n = ld32(t + 2); if (n >= r.n_cigar_raw && n < (1u << 29)) cg = (unsigned long long)(uintptr_t)(t + 6); }
+					cg = (unsigned long long)(uintptr_t)rec_cg_tag(r, n);
 				}
 				cg = __shfl(cg, 0); n = __shfl(n, 0);
 				if (cg) { r.cigar = (const uint8_t*)(uintptr_t)cg; r.n_cigar = n; }

@@ -397,6 +397,7 @@ protected:
 	void addInt(const std::string& n, const std::string& d, bool optional, int def = 0) { add(n, "int", d, optional, std::to_string(def)); }
 	void addFloat(const std::string& n, const std::string& d, bool optional, double def = 0.0) { add(n, "float", d, optional, number(def, 6)); }
 	void addFlag(const std::string& n, const std::string& d) { add(n, "flag", d, true, ""); }
+	void addString(const std::string& n, const std::string& d, bool optional, const std::string& def = "") { add(n, "string", d, optional, def); }
 	void addEnum(const std::string& n, const std::string& d, bool optional, const std::vector<std::string>& values, const std::string& def) { add(n, "enum", d, optional, def); params_.back().values = values; }
 	void changeLog(int y, int m, int d, const std::string& text) { char b[16]; snprintf(b, sizeof(b), "%04d-%02d-%02d", y, m, d); changelog_.push_back(std::string(b) + " " + text); }
 	std::string getInfile(const std::string& n) const { return get(n).value; }
@@ -405,6 +406,7 @@ protected:
 	int getInt(const std::string& n) const { return atoi(get(n).value.c_str()); }
 	double getFloat(const std::string& n) const { return atof(get(n).value.c_str()); }
 	bool getFlag(const std::string& n) const { return get(n).set; }
+	std::string getString(const std::string& n) const { return get(n).value; }
 	std::string getEnum(const std::string& n) const { return get(n).value; }
 	std::string appName() const { return fileName(args_.empty() ? "" : args_[0]); }
 	std::string settingsString(const std::string& key) const;   // <bin dir>/settings.ini "key = value"

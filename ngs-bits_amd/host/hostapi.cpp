@@ -2,6 +2,7 @@
 // BedFile / Chromosome code (load, sort, merge, chunk; BedFile.cpp / Chromosome.cpp of the reference), not from the oracle's BED loader - so the measured path and
 // the parity tests exercise host/core.cpp as well. Built as bin/libngsqc_hostapi.so; not part of the C ABI of include/ngsqc.h.
 #include "core.hpp"
+#include "Variant.hpp"
 #include <cstring>
 using namespace ngsbits;
 
@@ -31,4 +32,38 @@ long long ngsbits_bed_regions(const char* bed_path, const char* const* ref_names
 	catch (std::exception& e) { if (err && err_cap > 0) { strncpy(err, e.what(), (size_t)err_cap - 1); err[err_cap - 1] = 0; } return -1; }
 }
 
+
+static int fail(const std::exception& e, char* err, int err_cap) { if (err && err_cap > 0) { strncpy(err, e.what(), (size_t)err_cap - 1); err[err_cap - 1] = 0; } return -1; }
+
+// VcfFile::load (setAllowMultiSample(false)) + VcfFile::store of VcfAnnotateFrequency (host/Vcf.hpp). 0, or -1 with the message in err.
+int ngsbits_vcf_roundtrip(const char* in_path, const char* out_path, char* err, int err_cap)
+{
+	try { VcfFile v; v.load(in_path, false); v.store(out_path); return 0; }
+	catch (std::exception& e) { return fail(e, err, err_cap); }
+}
+
+// Variant(const VcfLine&) of a VCF line (pos, ref, alt; upper-cased as VcfFile::load does) and the window of getVariantDetails: *start / *end after normalize("-", true), ref / obs (64 bytes
+// each), and for an indel Variant::indelRegion over the FASTA (region = -1 / -1 for an SNV). 0, or -1 with the message in err.
+int ngsbits_variant_region(const char* fasta, const char* chr, int pos, const char* ref, const char* alt, int* start, int* end, char* ref_out, char* obs_out,
+                           int* reg_first, int* reg_second, char* err, int err_cap)
+{
+	try
+	{
+		VcfRecord r; r.chr = chr; r.pos = pos; r.ref = ref; r.alt = split(alt, ',');
+		for (auto& c : r.ref) c = (char)toupper((unsigned char)c);
+		for (auto& a : r.alt) for (auto& c : a) c = (char)toupper((unsigned char)c);   // (as VcfFile::load stores them)
+		const Variant v = Variant::fromVcf(r);
+		*start = v.start; *end = v.end;
+		snprintf(ref_out, 64, "%s", v.ref.c_str()); snprintf(obs_out, 64, "%s", v.obs.c_str());
+		*reg_first = *reg_second = -1;
+		if (!v.isSNV())
+		{
+			FastaFileIndex g(fasta); const Chromosome c(chr);
+			const std::pair<int, int> reg = variantIndelRegion(v.start, v.end, v.ref, v.obs, [&](int p, int l) { return g.seq(c, p, l); });
+			*reg_first = reg.first; *reg_second = reg.second;
+		}
+		return 0;
+	}
+	catch (std::exception& e) { return fail(e, err, err_cap); }
+}
 }
