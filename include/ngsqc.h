@@ -290,6 +290,20 @@ int ngsqc_set_cram_skip(int32_t flags);
 int32_t ngsqc_set_cram_skip_thread(int32_t flags);
 int ngsqc_cram_to_bam(const char* cram_path, const char* bam_path, const ngsqc_named_region* regions, int64_t n_regions);   /* regions NULL / 0: every record */
 
+/* ---- writing a BAM: BamFilter (src/BamFilter/main.cpp:71-134) over the BGZF writer of BamWriter (src/cppNGS/BamWriter.cpp). Records with flag 0x100 or 0x800
+ * are skipped; every other record, in file order, opens an entry for its exact read name or closes the open one (names that occur 3, 4, 5 times pair as
+ * (1,2), (3,4), ...). A closed pair in which both records pass alignment_pass (main.cpp:35-68, the thresholds below; -1 disables max_mm / max_gap / max_is) is
+ * written - the opener, then the closer, in the order of the closing records - and counted as passed, otherwise as dropped; entries still open at the end are
+ * dropped silently. The output is the input's header bytes in members of their own, then the kept records byte for byte (a record whose CIGAR came from a CG
+ * tag is written as htslib's bam_write1 writes it: see DESIGN.md) in BGZF members of 0xff00 bytes, then the EOF member. The pairing needs the whole file: a
+ * handle opened on a shard, a range, regions or the first records (BAM or CRAM) gives NGSQC_E_ARG. Open names are kept in device memory: NGSQC_E_DEVICE when
+ * they do not fit. The writer works in windows of about 1 GiB of the uncompressed output: its memory does not grow with the file. */
+typedef struct { int32_t min_mq, max_mq, max_mm, max_gap, min_dup, max_is; } ngsqc_pair_filter;
+int ngsqc_filter_pairs(ngsqc_handle* h, const ngsqc_pair_filter* p, const char* out_bam_path, int64_t* pairs_passed, int64_t* pairs_dropped);
+/* The encoder of that writer on a buffer: BGZF members of the 0xff00-byte pieces of in (dynamic Huffman DEFLATE, or a stored block where that is smaller), no
+ * EOF member; n == 0 gives no bytes. *out_n: the whole compressed size, also when it exceeds cap (then NGSQC_E_ARG, and out does not hold the result). Deterministic. */
+int ngsqc_bgzf_compress(const void* in, size_t n, int device, void* out, size_t cap, size_t* out_n);
+
 /* ---- writing the index. The reference never builds one: every indexed path above fails with "Could not load index of BAM/CRAM file"
  * (BamReader.cpp:742-746) until `samtools index` (htslib sam_index_build: hts_idx_push / hts_idx_finish / compress_binning, hts.c) has left a
  * <bam>.bai next to the BAM. ngsqc_write_bai writes that file (bai_path NULL: <path of the handle>.bai) from a handle on the whole BAM: one pass

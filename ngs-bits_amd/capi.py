@@ -77,6 +77,10 @@ ALLELE_NONE, ALLELE_INS, ALLELE_DEL = 0, 1, 2
 INDEL_COUNTER_NAMES = ("reads_mapped", "reads_mapq0", "depth", "n_ins", "n_del", "n_match")   # NGSQC_W_* order
 
 
+class PairFilter(C.Structure):
+    _fields_ = [("min_mq", C.c_int32), ("max_mq", C.c_int32), ("max_mm", C.c_int32), ("max_gap", C.c_int32), ("min_dup", C.c_int32), ("max_is", C.c_int32)]
+
+
 class JobResult(C.Structure):
     _fields_ = [("counters", C.c_void_p), ("gc_reads", C.c_void_p), ("site_counts", C.c_void_p), ("read_stats", C.c_void_p)]
 
@@ -151,6 +155,8 @@ def lib():
         L.ngsqc_site_pileup.restype = i32; L.ngsqc_site_pileup.argtypes = [vp, vp, i64, C.c_int32, C.c_int32, C.c_int32, vp]
         L.ngsqc_indel_windows.restype = i32; L.ngsqc_indel_windows.argtypes = [vp, vp, i64, C.c_int32, vp]
         L.ngsqc_variant_details.restype = i32; L.ngsqc_variant_details.argtypes = [vp, vp, i64, vp, i64, C.POINTER(VariantParams), vp, vp]
+        L.ngsqc_filter_pairs.restype = i32; L.ngsqc_filter_pairs.argtypes = [vp, C.POINTER(PairFilter), cp, C.POINTER(i64), C.POINTER(i64)]
+        L.ngsqc_bgzf_compress.restype = i32; L.ngsqc_bgzf_compress.argtypes = [vp, C.c_size_t, i32, vp, C.c_size_t, C.POINTER(C.c_size_t)]
         L.ngsqc_scan_reads.restype = i32; L.ngsqc_scan_reads.argtypes = [vp, C.c_int32, C.POINTER(ReadStats)]
         L.ngsqc_read_length_hist.restype = i32; L.ngsqc_read_length_hist.argtypes = [vp, vp, i64]
         L.ngsqc_read_cycle_stats.restype = i32; L.ngsqc_read_cycle_stats.argtypes = [vp, vp, i64]
@@ -180,6 +186,19 @@ def lib():
     return _lib
 
 
+def bgzf_compress(data, device=0):
+    """BGZF members of the 0xff00-byte pieces of data, deflated on the device (include/ngsqc.h ngsqc_bgzf_compress); no EOF member."""
+    data = bytes(data)
+    n = len(data)
+    cap = ((n + 0xff00 - 1) // 0xff00) * 65536
+    out = (C.c_uint8 * max(cap, 1))()
+    got = C.c_size_t(0)
+    rc = lib().ngsqc_bgzf_compress(data, n, int(device), C.cast(out, C.c_void_p), cap, C.byref(got))
+    if rc:
+        raise NgsqcError(rc, "bgzf_compress failed")
+    return bytes(out[:got.value])
+
+
 def device_count():
     """HIP devices the library's own runtime sees (include/ngsqc.h ngsqc_device_count) - not torch's: a second HIP / HSA runtime in the process is what a test that
     only wants a number must not load."""
@@ -196,6 +215,7 @@ EXPORTS = [
     "ngsqc_run_job", "ngsqc_depth_select", "ngsqc_depth_reduce", "ngsqc_region_read_counts", "ngsqc_upload_wait", "ngsqc_run_job_partial", "ngsqc_bai_range", "ngsqc_open_range", "ngsqc_header_text", "ngsqc_open_regions", "ngsqc_open_head",
     "ngsqc_write_bai", "ngsqc_bai_assemble", "ngsqc_bgzf_scan", "ngsqc_write_csi", "ngsqc_csi_assemble", "ngsqc_bai_ranges",
     "ngsqc_set_reference", "ngsqc_set_cram_skip", "ngsqc_set_cram_skip_thread", "ngsqc_cram_to_bam", "ngsqc_indel_windows", "ngsqc_variant_details",
+    "ngsqc_filter_pairs", "ngsqc_bgzf_compress",
 ]
 
 
@@ -541,6 +561,13 @@ class Handle:
         self._chk(lib().ngsqc_variant_details(self.h, C.cast(sarr, C.c_void_p), ns, C.cast(warr, C.c_void_p), nw, C.byref(prm), sc.ctypes.data, wc.ctypes.data))
         del keep
         return sc[:ns], wc[:nw]
+
+    def filter_pairs(self, out_path, min_mq=30, max_mq=256, max_mm=4, max_gap=1, min_dup=0, max_is=-1):
+        """BamFilter (src/BamFilter/main.cpp) of the whole file into the BAM out_path (include/ngsqc.h ngsqc_filter_pairs). Returns (pairs passed, pairs dropped)."""
+        p = PairFilter(int(min_mq), int(max_mq), int(max_mm), int(max_gap), int(min_dup), int(max_is))
+        passed, dropped = C.c_int64(0), C.c_int64(0)
+        self._chk(lib().ngsqc_filter_pairs(self.h, C.byref(p), os.fsencode(out_path), C.byref(passed), C.byref(dropped)))
+        return int(passed.value), int(dropped.value)
 
     # ---- one BAM sharded over several handles (include/ngsqc.h, "sharded" section) ----
     def scan_mapping_partial(self, mode, **kw):

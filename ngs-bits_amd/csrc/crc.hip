@@ -14,27 +14,12 @@
 // of it (virtual lanes l, l + 64, ..): K independent chains whose lookups and loads are in flight together. The K states of a lane fold into one with the constant
 // map "advance over 4 KiB of zero bytes" (S = adv(adv(adv(s0) ^ s1) ^ s2) ^ s3), so the end of a member costs one GF(2) multiplication per lane as before.
 #include "common.h"
+#include "crc_dev.h"
 #include <mutex>
 
 namespace ngsqc {
 
 namespace {
-constexpr uint32_t CRC_POLY = 0xEDB88320u;   // reflected CRC-32 (gzip)
-constexpr int CRC_ROUND = 4096, CRC_PIECE = 64;
-constexpr int TAB_SLICE = 0, TAB_GAP = 1024, TAB_LANE = 2048, TAB_INIT = 2048 + 64, TAB_GAP2 = TAB_INIT + 65537, TAB_GAP4 = TAB_GAP2 + 1024, TAB_ADV = TAB_GAP4 + 1024, TAB_TOTAL = TAB_ADV + 1024;
-// TAB_GAP / TAB_GAP2 / TAB_GAP4: a state advanced over the zero bytes between a chain's pieces in rounds of 4 / 8 / 16 KiB; TAB_ADV: over 4 KiB (folds a lane's chains)
-
-__device__ __forceinline__ uint32_t gf_mul(uint32_t a, uint32_t b)   // a * b mod P, reflected representation (x^0 = 0x80000000)
-{
-	uint32_t p = 0;
-	#pragma unroll
-	for (int i = 31; i >= 0; --i)
-	{
-		p ^= (a >> i) & 1u ? b : 0u;
-		b = (b >> 1) ^ ((b & 1u) ? CRC_POLY : 0u);
-	}
-	return p;
-}
 
 __global__ __launch_bounds__(256) void crc32_kernel(const BlockDesc* __restrict__ blocks, int64_t n_blocks, const uint8_t* __restrict__ out_base,
                                                     const uint32_t* __restrict__ expected, BlockStatus* __restrict__ status, const uint32_t* __restrict__ tabs)
@@ -264,7 +249,9 @@ const std::vector<uint32_t>& host_tables()
 	});
 	return tab;
 }
-const uint32_t* device_tables()
+} // namespace
+
+const uint32_t* crc_device_tables()
 {
 	static std::mutex mu; static uint32_t* d_tab[64] = {nullptr};
 	int dev = 0; if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) throw std::runtime_error("invalid HIP device for the CRC tables");
@@ -277,12 +264,11 @@ const uint32_t* device_tables()
 	}
 	return d_tab[dev];
 }
-} // namespace
 
 void launch_crc32(const BlockDesc* d_blocks, int64_t n_blocks, const uint8_t* d_out, const uint32_t* d_expected, BlockStatus* d_status, hipStream_t s)
 {
 	if (n_blocks <= 0) return;
-	const uint32_t* tabs = device_tables();
+	const uint32_t* tabs = crc_device_tables();
 	const int64_t wgs = (n_blocks + 3) / 4;
 	const char* e = getenv("NGSQC_CRC_CHAINS"); const int chains = e && (atoi(e) == 1 || atoi(e) == 2) ? atoi(e) : 4;   // chains per lane (1: the round-2 kernel); read per launch so that one process can compare them
 	const dim3 grid((unsigned)(wgs < 32768 ? wgs : 32768)), wg(256);

@@ -160,6 +160,7 @@ struct ngsqc_handle
 {
 	std::string err, path;
 	bool from_cram = false;                        // the image is the BAM stream the host made of a CRAM 3.0 file (cram.hip)
+	bool selection = false;                        // opened for a range, regions or the first records (a CRAM keeps only the slices they need, and is then laid out like a whole file)
 	int device = 0; int n_cu = 256;
 	hipStream_t stream = nullptr;                 // main stream: K2, consumers, setup copies
 	hipStream_t s_p1[2] = {nullptr, nullptr};      // K1 phase 1 (alternating: the next chunk's waves fill in as the previous chunk's finish)
@@ -295,6 +296,18 @@ void sync_all(ngsqc_handle* h);
 // Visit every tile in file order with the tile resident in HBM; f returns false to stop early
 void stream_tiles(ngsqc_handle* h, const std::function<bool(const TileCtx&)>& f);
 void for_each_tile(ngsqc_handle* h, const std::function<bool(int)>& f);
+
+// ---- deflate.hip: the BGZF writer's encoder ----
+constexpr int64_t BGZF_PIECE = 0xff00;   // uncompressed bytes of a BGZF member as htslib's bgzf_write cuts the stream
+size_t bgzf_max_bytes(int64_t n);        // bytes the members of n input bytes may take (a 64 KiB slot each)
+// deflates whole pieces of BGZF_PIECE bytes (the last one may be short) into members, compacted; scratch kept across calls
+struct BgzfDeflater
+{
+	DevBuf<uint16_t> prev; DevBuf<uint32_t> tok, sizes; DevBuf<uint64_t> off; DevBuf<uint8_t> slots, scan_tmp;
+	int grid = 0; int64_t cap_members = 0;
+	void reserve(int64_t max_members, int device);
+	size_t run(const uint8_t* d_in, int64_t n, uint8_t* d_out, hipStream_t s, int device);   // returns the compressed size (waits for s)
+};
 
 // ---- jobs.hip: the consumers of a tile and the jobs made of them ----
 void write_bai(ngsqc_handle* h, const char* out_path, bool csi = false, int min_shift = 14);

@@ -807,6 +807,7 @@ int open_impl(ngsqc_handle** out, const char* path, const void* bytes, size_t n,
 		if (!bytes && n) throw ArgError("null BAM buffer");
 		// CRAM 3.0 (BamReader.cpp:482-492): the container layer is decoded on the host (cram.hip) into a BAM stream in stored BGZF members; from here on the file is a BAM
 		// image in memory. Index-driven requests (a .crai names slices, not BGZF members) fall back to the whole file: a superset of what a region needs.
+		if (range) h->selection = true;
 		ByteImage cram_image; CramQualPlan qplan; const uint8_t* cram_src = nullptr;
 		const bool from_cram = is_cram((const uint8_t*)bytes, n);
 		if (from_cram)

@@ -70,6 +70,23 @@ __device__ static const uint8_t* aux_find(const uint8_t* p, const uint8_t* end, 
 	return nullptr;
 }
 
+// BamAlignment::tagi (src/cppNGS/BamReader.cpp:286-297: bam_aux2i): a missing tag and a tag of a non-integer type count as 0
+__device__ static int aux_tagi(const RecView& r, uint8_t t0, uint8_t t1)
+{
+	const uint8_t* t = aux_find(rec_aux(r), rec_end(r), t0, t1);
+	if (!t) return 0;
+	switch (*t)
+	{
+		case 'c': return (int8_t)t[1];
+		case 'C': return t[1];
+		case 's': return (int16_t)ld16(t + 1);
+		case 'S': return ld16(t + 1);
+		case 'i': return (int32_t)ld32(t + 1);
+		case 'I': return (int)ld32(t + 1);
+		default: return 0;
+	}
+}
+
 __device__ __forceinline__ long long wave_sum(long long v)
 {
 	for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);

@@ -41,23 +41,6 @@ struct Acc
 	int ns_tid = -2; bool ns_val = false;   // tid_nonspecial[ns_tid] (round 5: one dependent load per record less - a walker changes reference a few times per file)
 };
 
-// BamAlignment::tagi (BamReader.cpp:286-297)
-__device__ static int aux_tagi(const RecView& r, uint8_t t0, uint8_t t1)
-{
-	const uint8_t* t = aux_find(rec_aux(r), rec_end(r), t0, t1);
-	if (!t) return 0;
-	switch (*t)
-	{
-		case 'c': return (int8_t)t[1];
-		case 'C': return t[1];
-		case 's': return (int16_t)ld16(t + 1);
-		case 'S': return ld16(t + 1);
-		case 'i': return (int32_t)ld32(t + 1);
-		case 'I': return (int)ld32(t + 1);
-		default: return 0;
-	}
-}
-
 // first region index in [first,last) with reg_end >= s  (merged regions: ends are sorted too)
 __device__ __forceinline__ int lower_region(const int32_t* __restrict__ reg_end, int first, int last, int s)
 {

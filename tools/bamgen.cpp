@@ -33,7 +33,7 @@ struct Params
 {
 	int64_t n_reads; uint64_t seed; int mode;       // mode 0 = short-read WGS, 1 = long-read
 	double depth; int first_contig; int level; int aligned; int threads; int64_t start_pos;
-	int flavor = 0;   // bit 0: SEQ from a synthetic reference genome (overlapping reads share sequence, 0.5 % mismatches); bits 1-2: quality model 0 = 4 levels, 1 = 8 levels (NovaSeq-style bins), 2 = 40 levels (HiSeq-style decay)
+	int flavor = 0;   // bit 0: SEQ from a synthetic reference genome (overlapping reads share sequence, 0.5 % mismatches); bits 1-2: quality model 0 = 4 levels, 1 = 8 levels (NovaSeq-style bins), 2 = 40 levels (HiSeq-style decay); bit 3: mates share read names (BamFilter)
 };
 
 void put32(std::vector<uint8_t>& v, uint32_t x) { v.push_back(x & 255); v.push_back((x >> 8) & 255); v.push_back((x >> 16) & 255); v.push_back((x >> 24) & 255); }
@@ -167,7 +167,16 @@ void short_read(std::vector<uint8_t>& r, Rng& g, int32_t tid, int32_t pos, int64
 	if (g.uni() < 0.08 && !unmapped) flag |= 0x400;
 	if (unmapped) flag |= 0x4; if (secondary) flag |= 0x100; if (supp) flag |= 0x800;
 	uint8_t mapq = unmapped ? 0 : draw_mapq(g);
-	char name[48]; int nl = snprintf(name, sizeof(name), "A00%03u:%u:H%05XDSXY:%u:%04u:%05u:%05u", (unsigned)(serial % 7) + 100, 45u + (unsigned)(serial % 3), (unsigned)((serial >> 20) & 0xFFFFF), 1 + (unsigned)(serial % 4), 1101 + (unsigned)g.below(1578), (unsigned)g.below(32000), (unsigned)g.below(32000));
+	const unsigned ny = (unsigned)g.below(32000), nx = (unsigned)g.below(32000), tile = 1101 + (unsigned)g.below(1578);   // (drawn in the order g++ evaluated them as arguments: the files of flavors 0-7 stay as they were)
+	char name[48]; int nl;
+	if (flavor & 8)
+	{
+		// mates: records s and s + 1024 of every block of 2048 (file order) share the name of their pair, a fragment's two reads ~1000 records apart
+		const uint64_t pr = serial / 2048 * 1024 + serial % 1024;
+		uint64_t x = pr * 0x9E3779B97F4A7C15ull; x ^= x >> 29; x *= 0xBF58476D1CE4E5B9ull; x ^= x >> 32;
+		nl = snprintf(name, sizeof(name), "A00%03u:%u:H%05XDSXY:%u:%04u:%05u:%05u", (unsigned)(pr % 7) + 100, 45u + (unsigned)(pr % 3), (unsigned)((pr >> 20) & 0xFFFFF), 1 + (unsigned)(pr % 4), 1101 + (unsigned)(x % 1578), (unsigned)((x >> 16) % 32000), (unsigned)((x >> 32) % 32000));
+	}
+	else nl = snprintf(name, sizeof(name), "A00%03u:%u:H%05XDSXY:%u:%04u:%05u:%05u", (unsigned)(serial % 7) + 100, 45u + (unsigned)(serial % 3), (unsigned)((serial >> 20) & 0xFFFFF), 1 + (unsigned)(serial % 4), tile, nx, ny);
 	// CIGAR
 	uint32_t cig[6]; int nc = 0; int ref_len = len; int nm = (int)g.below(3);
 	if (!unmapped)
