@@ -303,6 +303,22 @@ int ngsqc_filter_pairs(ngsqc_handle* h, const ngsqc_pair_filter* p, const char* 
 /* The encoder of that writer on a buffer: BGZF members of the 0xff00-byte pieces of in (dynamic Huffman DEFLATE, or a stored block where that is smaller), no
  * EOF member; n == 0 gives no bytes. *out_n: the whole compressed size, also when it exceeds cap (then NGSQC_E_ARG, and out does not hold the result). Deterministic. */
 int ngsqc_bgzf_compress(const void* in, size_t n, int device, void* out, size_t cap, size_t* out_n);
+/* The same encoder at a compression level: 0 stored blocks, 1-3 a fast greedy parse (short hash chains, no lazy step), 4-9 the parse of ngsqc_bgzf_compress
+ * (byte-identical to it). Deterministic at every level. NGSQC_E_ARG for a level outside 0..9. */
+int ngsqc_bgzf_compress_level(const void* in, size_t n, int device, int level, void* out, size_t cap, size_t* out_n);
+
+/* ---- BamToFastq (src/BamToFastq/main.cpp:77-214): the records of the handle in file order, secondary and supplementary records skipped; with remove_duplicates
+ * the duplicates skipped and counted; with fix a record whose (name, read 1) pair came earlier in the file dropped and counted (the set of seen pairs lives in
+ * device memory for the whole run). Paired-end mode (out2 not NULL and not ""): unpaired records are skipped and counted, the others are joined by read name
+ * (the mate cache); a pair goes out when its second record comes, the read-1 record to out1, the other to out2. Single-end mode: every record to out1.
+ * An entry is "@name\nBASES\n+\nQUALS\n" as gzputs writes it (a quality byte of 0 ends its line); a reverse-strand record is reverse-complemented; extend > 0
+ * pads with 'N' / '#' to that length. Both files are BGZF (valid gzip) at the given compression level (0-9), ending with the EOF member.
+ * reg_tid >= 0: only the records htslib's iterator returns for (reg_tid, reg_start, reg_end), 1-based closed (a handle from ngsqc_open_regions, or the whole
+ * file). A handle on a shard or a range without a region is NGSQC_E_ARG. A reverse-strand record that would be written and holds a base other than ACGTN:
+ * NGSQC_E_FORMAT "Could not convert base 'X' to complement!" for the first such entry in output order. max_cached: the largest number of open names. */
+typedef struct { int32_t remove_duplicates, fix, extend, compression_level; int32_t reg_tid, reg_start, reg_end; } ngsqc_fastq_params;
+typedef struct { int64_t paired, unpaired, unmatched, single_end, duplicates, fixed, max_cached; } ngsqc_fastq_counts;
+int ngsqc_bam_to_fastq(ngsqc_handle* h, const ngsqc_fastq_params* p, const char* out1, const char* out2, ngsqc_fastq_counts* c);
 
 /* ---- writing the index. The reference never builds one: every indexed path above fails with "Could not load index of BAM/CRAM file"
  * (BamReader.cpp:742-746) until `samtools index` (htslib sam_index_build: hts_idx_push / hts_idx_finish / compress_binning, hts.c) has left a

@@ -81,6 +81,18 @@ class PairFilter(C.Structure):
     _fields_ = [("min_mq", C.c_int32), ("max_mq", C.c_int32), ("max_mm", C.c_int32), ("max_gap", C.c_int32), ("min_dup", C.c_int32), ("max_is", C.c_int32)]
 
 
+class FastqParams(C.Structure):
+    _fields_ = [("remove_duplicates", C.c_int32), ("fix", C.c_int32), ("extend", C.c_int32), ("compression_level", C.c_int32),
+                ("reg_tid", C.c_int32), ("reg_start", C.c_int32), ("reg_end", C.c_int32)]
+
+
+FASTQ_COUNT_NAMES = ("paired", "unpaired", "unmatched", "single_end", "duplicates", "fixed", "max_cached")
+
+
+class FastqCounts(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in FASTQ_COUNT_NAMES]
+
+
 class JobResult(C.Structure):
     _fields_ = [("counters", C.c_void_p), ("gc_reads", C.c_void_p), ("site_counts", C.c_void_p), ("read_stats", C.c_void_p)]
 
@@ -157,6 +169,8 @@ def lib():
         L.ngsqc_variant_details.restype = i32; L.ngsqc_variant_details.argtypes = [vp, vp, i64, vp, i64, C.POINTER(VariantParams), vp, vp]
         L.ngsqc_filter_pairs.restype = i32; L.ngsqc_filter_pairs.argtypes = [vp, C.POINTER(PairFilter), cp, C.POINTER(i64), C.POINTER(i64)]
         L.ngsqc_bgzf_compress.restype = i32; L.ngsqc_bgzf_compress.argtypes = [vp, C.c_size_t, i32, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+        L.ngsqc_bgzf_compress_level.restype = i32; L.ngsqc_bgzf_compress_level.argtypes = [vp, C.c_size_t, i32, i32, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+        L.ngsqc_bam_to_fastq.restype = i32; L.ngsqc_bam_to_fastq.argtypes = [vp, C.POINTER(FastqParams), cp, cp, C.POINTER(FastqCounts)]
         L.ngsqc_scan_reads.restype = i32; L.ngsqc_scan_reads.argtypes = [vp, C.c_int32, C.POINTER(ReadStats)]
         L.ngsqc_read_length_hist.restype = i32; L.ngsqc_read_length_hist.argtypes = [vp, vp, i64]
         L.ngsqc_read_cycle_stats.restype = i32; L.ngsqc_read_cycle_stats.argtypes = [vp, vp, i64]
@@ -186,14 +200,18 @@ def lib():
     return _lib
 
 
-def bgzf_compress(data, device=0):
-    """BGZF members of the 0xff00-byte pieces of data, deflated on the device (include/ngsqc.h ngsqc_bgzf_compress); no EOF member."""
+def bgzf_compress(data, device=0, level=None):
+    """BGZF members of the 0xff00-byte pieces of data, deflated on the device (include/ngsqc.h ngsqc_bgzf_compress); no EOF member.
+    level None: ngsqc_bgzf_compress; 0-9: ngsqc_bgzf_compress_level (0 stored, 1-3 the fast parse, 4-9 the default parse)."""
     data = bytes(data)
     n = len(data)
     cap = ((n + 0xff00 - 1) // 0xff00) * 65536
     out = (C.c_uint8 * max(cap, 1))()
     got = C.c_size_t(0)
-    rc = lib().ngsqc_bgzf_compress(data, n, int(device), C.cast(out, C.c_void_p), cap, C.byref(got))
+    if level is None:
+        rc = lib().ngsqc_bgzf_compress(data, n, int(device), C.cast(out, C.c_void_p), cap, C.byref(got))
+    else:
+        rc = lib().ngsqc_bgzf_compress_level(data, n, int(device), int(level), C.cast(out, C.c_void_p), cap, C.byref(got))
     if rc:
         raise NgsqcError(rc, "bgzf_compress failed")
     return bytes(out[:got.value])
@@ -215,7 +233,7 @@ EXPORTS = [
     "ngsqc_run_job", "ngsqc_depth_select", "ngsqc_depth_reduce", "ngsqc_region_read_counts", "ngsqc_upload_wait", "ngsqc_run_job_partial", "ngsqc_bai_range", "ngsqc_open_range", "ngsqc_header_text", "ngsqc_open_regions", "ngsqc_open_head",
     "ngsqc_write_bai", "ngsqc_bai_assemble", "ngsqc_bgzf_scan", "ngsqc_write_csi", "ngsqc_csi_assemble", "ngsqc_bai_ranges",
     "ngsqc_set_reference", "ngsqc_set_cram_skip", "ngsqc_set_cram_skip_thread", "ngsqc_cram_to_bam", "ngsqc_indel_windows", "ngsqc_variant_details",
-    "ngsqc_filter_pairs", "ngsqc_bgzf_compress",
+    "ngsqc_filter_pairs", "ngsqc_bgzf_compress", "ngsqc_bgzf_compress_level", "ngsqc_bam_to_fastq",
 ]
 
 
@@ -568,6 +586,22 @@ class Handle:
         passed, dropped = C.c_int64(0), C.c_int64(0)
         self._chk(lib().ngsqc_filter_pairs(self.h, C.byref(p), os.fsencode(out_path), C.byref(passed), C.byref(dropped)))
         return int(passed.value), int(dropped.value)
+
+    def to_fastq(self, out1, out2=None, remove_duplicates=False, extend=0, fix=False, compression_level=1, region=None):
+        """BamToFastq (src/BamToFastq/main.cpp) into the gzip files out1 (and out2: paired-end mode; None: single-end) (include/ngsqc.h ngsqc_bam_to_fastq).
+        region: (chromosome name or tid, start, end), 1-based closed. Returns the counts as a dict (FASTQ_COUNT_NAMES)."""
+        p = FastqParams(int(bool(remove_duplicates)), int(bool(fix)), int(extend), int(compression_level), -1, 0, 0)
+        if region is not None:
+            c, a, b = region
+            if not isinstance(c, int):
+                names = [n for n, _ in self.refs]
+                if c not in names:
+                    raise NgsqcError(-1, f"unknown chromosome '{c}'")
+                c = names.index(c)
+            p.reg_tid, p.reg_start, p.reg_end = int(c), int(a), int(b)
+        cnt = FastqCounts()
+        self._chk(lib().ngsqc_bam_to_fastq(self.h, C.byref(p), os.fsencode(out1), os.fsencode(out2) if out2 else None, C.byref(cnt)))
+        return {n: int(getattr(cnt, n)) for n in FASTQ_COUNT_NAMES}
 
     # ---- one BAM sharded over several handles (include/ngsqc.h, "sharded" section) ----
     def scan_mapping_partial(self, mode, **kw):

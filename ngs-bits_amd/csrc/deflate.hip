@@ -165,13 +165,14 @@ __device__ __forceinline__ int token_bits(Lds& S, uint32_t t, bool emit, uint32_
 	return l1 + e1 + l2 + e2;
 }
 
-// longest match at p (limit: bytes that may be matched) along the chain; returns len (0: none) and dist
+// longest match at p (limit: bytes that may be matched) along the chain, at most CHAIN candidates; returns len (0: none) and dist
+template <int CHAIN, int NICE_LEN>
 __device__ __forceinline__ int find_match(const Lds& S, const uint16_t* __restrict__ prev, int p, int limit, int& dist)
 {
 	if (limit < 3) return 0;
 	limit = min(limit, 258);
 	int best = 2, bd = 0, c = prev[p], depth = 0;
-	while (c && depth++ < MAX_CHAIN)
+	while (c && depth++ < CHAIN)
 	{
 		const int q = c - 1;
 		if (p - q > WINDOW) break;
@@ -179,7 +180,7 @@ __device__ __forceinline__ int find_match(const Lds& S, const uint16_t* __restri
 		{
 			int l = 0;
 			while (l < limit && in_byte(S, q + l) == in_byte(S, p + l)) ++l;
-			if (l > best) { best = l; bd = p - q; if (l >= NICE || l == limit) break; }
+			if (l > best) { best = l; bd = p - q; if (l >= NICE_LEN || l == limit) break; }
 		}
 		c = prev[q];
 	}
@@ -187,6 +188,9 @@ __device__ __forceinline__ int find_match(const Lds& S, const uint16_t* __restri
 	dist = bd; return best;
 }
 
+// The parse of a compression level (ngsqc_bgzf_compress_level): CHAIN candidates per position, a match of NICE_LEN bytes ends the search, LAZY_STEP: zlib's lazy
+// step; STORE: stored blocks only (level 0). Levels 4-9 and the default are <MAX_CHAIN, NICE, true, false> (the parse of ngsqc_bgzf_compress).
+template <int CHAIN, int NICE_LEN, bool LAZY_STEP, bool STORE>
 __global__ __launch_bounds__(NT) void bgzf_deflate_kernel(const uint8_t* __restrict__ in, int64_t n_total, int64_t n_members, uint8_t* __restrict__ slots, uint32_t* __restrict__ sizes,
                                                             uint16_t* __restrict__ prev_all, uint32_t* __restrict__ tok_all, const uint32_t* __restrict__ tabs)
 {
@@ -222,6 +226,8 @@ __global__ __launch_bounds__(NT) void bgzf_deflate_kernel(const uint8_t* __restr
 			for (int o = 32; o > 0; o >>= 1) v ^= (uint32_t)__shfl_xor((int)v, o);
 			if ((t & 63) == 0) atomicXor(&S.crc, v);
 		}
+		if constexpr (STORE) { if (t == 0) S.stored = 1u; }
+		else {
 		// ---- 2. hash chains ----
 		for (int r0 = 0; r0 < n; r0 += NT)
 		{
@@ -249,14 +255,14 @@ __global__ __launch_bounds__(NT) void bgzf_deflate_kernel(const uint8_t* __restr
 		{
 			const int s0 = t * SEGLEN, s1 = min(n, s0 + SEGLEN);
 			uint32_t* o = tok + s0; int k = 0;
-			int p = s0, dist = 0, len = p < s1 ? find_match(S, prev, p, s1 - p, dist) : 0;
+			int p = s0, dist = 0, len = p < s1 ? find_match<CHAIN, NICE_LEN>(S, prev, p, s1 - p, dist) : 0;
 			while (p < s1)
 			{
 				if (len >= 3)
 				{
-					if (len < LAZY && p + 1 < s1)
+					if (LAZY_STEP && len < LAZY && p + 1 < s1)
 					{
-						int d1 = 0; const int l1 = find_match(S, prev, p + 1, s1 - p - 1, d1);
+						int d1 = 0; const int l1 = find_match<CHAIN, NICE_LEN>(S, prev, p + 1, s1 - p - 1, d1);
 						if (l1 > len)
 						{
 							o[k++] = in_byte(S, p); atomicAdd(&S.freq[in_byte(S, p)], 1u);
@@ -268,7 +274,7 @@ __global__ __launch_bounds__(NT) void bgzf_deflate_kernel(const uint8_t* __restr
 					p += len;
 				}
 				else { o[k++] = in_byte(S, p); atomicAdd(&S.freq[in_byte(S, p)], 1u); ++p; }
-				len = p < s1 ? find_match(S, prev, p, s1 - p, dist) : 0;
+				len = p < s1 ? find_match<CHAIN, NICE_LEN>(S, prev, p, s1 - p, dist) : 0;
 			}
 			S.seg_ntok[t] = (uint32_t)k;
 		}
@@ -345,10 +351,11 @@ __global__ __launch_bounds__(NT) void bgzf_deflate_kernel(const uint8_t* __restr
 			S.seg_bits[NSEG] = acc; S.total_bits = acc;
 			S.stored = (acc + 7) / 8 >= (uint32_t)n + 5 ? 1u : 0u;   // (a stored block: 5 bytes of framing; PIECE + 5 + 26 <= SLOT)
 		}
+		}   // (!STORE)
 		__syncthreads();
 		const bool stored = S.stored != 0;
 		uint32_t zbytes;
-		if (!stored)
+		if (!STORE && !stored)
 		{
 			for (int i = t; i < SLOT / 4 + 2; i += NT) S.buf[i] = 0;
 			__syncthreads();
@@ -422,14 +429,21 @@ void BgzfDeflater::reserve(int64_t max_members, int device)
 	cap_members = max_members;
 }
 
-// compresses n bytes at d_in (n <= cap_members pieces) into d_out (bgzf_max_bytes(n) bytes); returns the compressed size (waits for the stream)
-size_t BgzfDeflater::run(const uint8_t* d_in, int64_t n, uint8_t* d_out, hipStream_t s, int device)
+// compresses n bytes at d_in (n <= cap_members pieces) into d_out (bgzf_max_bytes(n) bytes) at a compression level (0: stored, 1-3: the fast parse, anything else:
+// the default parse); returns the compressed size (waits for the stream)
+size_t BgzfDeflater::run(const uint8_t* d_in, int64_t n, uint8_t* d_out, hipStream_t s, int device, int level)
 {
 	if (n <= 0) return 0;
 	const int64_t nm = (n + PIECE - 1) / PIECE;
 	if (nm > cap_members || !grid) reserve(nm, device);
 	const int g = (int)std::min<int64_t>(nm, grid);
-	hipLaunchKernelGGL(bgzf_deflate_kernel, dim3(g), dim3(NT), 0, s, d_in, n, nm, slots.p, sizes.p, prev.p, tok.p, crc_device_tables()); KCHECK();
+	const uint32_t* tabs = crc_device_tables();
+	if (level == 0) hipLaunchKernelGGL((bgzf_deflate_kernel<1, 1, false, true>), dim3(g), dim3(NT), 0, s, d_in, n, nm, slots.p, sizes.p, prev.p, tok.p, tabs);
+	else if (level == 1) hipLaunchKernelGGL((bgzf_deflate_kernel<4, 32, false, false>), dim3(g), dim3(NT), 0, s, d_in, n, nm, slots.p, sizes.p, prev.p, tok.p, tabs);
+	else if (level == 2) hipLaunchKernelGGL((bgzf_deflate_kernel<8, 64, false, false>), dim3(g), dim3(NT), 0, s, d_in, n, nm, slots.p, sizes.p, prev.p, tok.p, tabs);
+	else if (level == 3) hipLaunchKernelGGL((bgzf_deflate_kernel<16, 64, false, false>), dim3(g), dim3(NT), 0, s, d_in, n, nm, slots.p, sizes.p, prev.p, tok.p, tabs);
+	else hipLaunchKernelGGL((bgzf_deflate_kernel<MAX_CHAIN, NICE, true, false>), dim3(g), dim3(NT), 0, s, d_in, n, nm, slots.p, sizes.p, prev.p, tok.p, tabs);
+	KCHECK();
 	size_t tb = scan_tmp.n;
 	if (rocprim::exclusive_scan(scan_tmp.p, tb, sizes.p, off.p, (uint64_t)0, (size_t)nm + 0, rocprim::plus<uint64_t>(), s) != hipSuccess) throw std::runtime_error("rocprim::exclusive_scan failed");
 	hipLaunchKernelGGL(bgzf_compact_kernel, dim3((unsigned)std::min<int64_t>(nm, 4096)), dim3(256), 0, s, slots.p, sizes.p, off.p, nm, d_out); KCHECK();
@@ -444,7 +458,8 @@ size_t BgzfDeflater::run(const uint8_t* d_in, int64_t n, uint8_t* d_out, hipStre
 } // namespace ngsqc
 
 // BGZF members of 0xff00-byte pieces of the input, no EOF member (include/ngsqc.h)
-int ngsqc_bgzf_compress(const void* in, size_t n, int device, void* out, size_t cap, size_t* out_n)
+namespace {
+int bgzf_compress_impl(const void* in, size_t n, int device, int level, void* out, size_t cap, size_t* out_n)
 {
 	if ((n && !in) || !out_n || (cap && !out)) return NGSQC_E_ARG;
 	*out_n = 0;
@@ -466,7 +481,7 @@ int ngsqc_bgzf_compress(const void* in, size_t n, int device, void* out, size_t 
 		{
 			const int64_t k = std::min<int64_t>(WIN, (int64_t)n - o);
 			HIPCHK(hipMemcpyAsync(d_in.p, (const uint8_t*)in + o, (size_t)k, hipMemcpyHostToDevice, s));
-			const size_t z_n = z.run(d_in.p, k, d_out.p, s, device);
+			const size_t z_n = z.run(d_in.p, k, d_out.p, s, device, level);
 			over = over || done + z_n > cap;   // (past cap the windows are still compressed, for the size)
 			if (!over)
 			{
@@ -479,4 +494,13 @@ int ngsqc_bgzf_compress(const void* in, size_t n, int device, void* out, size_t 
 		return over ? NGSQC_E_ARG : NGSQC_OK;
 	}
 	catch (std::exception& e) { fprintf(stderr, "ngsqc_bgzf_compress: %s\n", e.what()); return NGSQC_E_DEVICE; }
+}
+} // namespace
+
+int ngsqc_bgzf_compress(const void* in, size_t n, int device, void* out, size_t cap, size_t* out_n) { return bgzf_compress_impl(in, n, device, -1, out, cap, out_n); }
+
+int ngsqc_bgzf_compress_level(const void* in, size_t n, int device, int level, void* out, size_t cap, size_t* out_n)
+{
+	if (level < 0 || level > 9) return NGSQC_E_ARG;
+	return bgzf_compress_impl(in, n, device, level, out, cap, out_n);
 }

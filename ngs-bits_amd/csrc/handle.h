@@ -306,7 +306,7 @@ struct BgzfDeflater
 	DevBuf<uint16_t> prev; DevBuf<uint32_t> tok, sizes; DevBuf<uint64_t> off; DevBuf<uint8_t> slots, scan_tmp;
 	int grid = 0; int64_t cap_members = 0;
 	void reserve(int64_t max_members, int device);
-	size_t run(const uint8_t* d_in, int64_t n, uint8_t* d_out, hipStream_t s, int device);   // returns the compressed size (waits for s)
+	size_t run(const uint8_t* d_in, int64_t n, uint8_t* d_out, hipStream_t s, int device, int level = -1);   // returns the compressed size (waits for s); level: 0 stored, 1-3 fast, else the default parse
 };
 
 // ---- jobs.hip: the consumers of a tile and the jobs made of them ----

@@ -1,0 +1,325 @@
+// The mate join by read name and the windowed BGZF writer, shared by the tools that pair records and write compressed output (BamFilter: pairs.hip,
+// BamToFastq: fastq.hip). One pass over the tiles; per tile (NameJoin):
+//   1. the tool's keys kernel gives every tile record a 64-bit name hash (KEY_NONE: the record takes no part), its source pointer and a 32-bit info word whose
+//      bit 31 says the record is kept ("passes"); val[e] = e for every entry.
+//   2. sort: the open entries carried over from earlier tiles ("held", in (hash, ordinal) order) followed by the tile's records, radix-sorted by hash (rocPRIM,
+//      stable: within a hash the order stays the file order).
+//   3. resolve: one thread per run of equal hashes. When every name of the run is the same, the run pairs (0,1), (2,3), ... and an odd last entry stays open;
+//      otherwise (a hash collision) the run is paired name by name in file order. close_of[closer] = opener entry << 1 | kept (both pass); counts[0] / [1]:
+//      pairs kept / not kept.
+//   4. held: the entries still open are compacted; their bytes are copied out of the tile buffer (the whole record if it passes, the name alone if not).
+// BgzfStream cuts one output stream into windows of whole 0xff00-byte pieces: the tool fills a window, its whole pieces go through the encoder (deflate.hip)
+// and a host thread writes the members while the next window is filled; the partial piece moves to the front.
+#pragma once
+#include "handle.h"
+#include "rec.h"
+#include <rocprim/device/device_radix_sort.hpp>
+#include <rocprim/device/device_scan.hpp>
+
+namespace ngsqc {
+namespace {
+constexpr uint64_t KEY_NONE = ~0ull;
+
+__device__ __forceinline__ uint64_t name_hash(const uint8_t* p, int n)   // FNV-1a, then a 64-bit finaliser (splitmix64)
+{
+	uint64_t h = 0xcbf29ce484222325ull;
+	for (int i = 0; i < n; ++i) h = (h ^ p[i]) * 0x100000001b3ull;
+	h ^= h >> 30; h *= 0xbf58476d1ce4e5b9ull; h ^= h >> 27; h *= 0x94d049bb133111ebull; h ^= h >> 31;
+	return h;
+}
+
+// test hook NGSQC_NAME_HASH_BITS: fewer hash bits, collisions everywhere
+inline uint64_t name_hash_mask()
+{
+	const char* hb = getenv("NGSQC_NAME_HASH_BITS");
+	const int bits = hb ? std::max(1, std::min(63, atoi(hb))) : 63;
+	return bits >= 63 ? (~0ull >> 1) : ((1ull << bits) - 1);
+}
+
+__device__ __forceinline__ bool same_name(const uint8_t* a, const uint8_t* b)
+{
+	const uint32_t la = a[12], lb = b[12];
+	if (la != lb) return false;
+	for (uint32_t i = 0; i < la; ++i) if (a[36 + i] != b[36 + i]) return false;
+	return true;
+}
+
+struct ResolveOut { int64_t* close_of; uint8_t* held; uint8_t* st; unsigned long long* counts; };   // close_of[tile record] = opener entry << 1 | kept; held / st: per sorted position
+
+__device__ __forceinline__ void close_pair(const ResolveOut& o, const uint32_t* info, int64_t H, uint32_t oe, uint32_t ce)
+{
+	const bool kept = (info[oe] >> 31) && (info[ce] >> 31);
+	o.close_of[ce - H] = (int64_t)oe << 1 | (kept ? 1 : 0);   // (a closer is always a tile record: every held entry lies before the tile)
+	atomicAdd(&o.counts[kept ? 0 : 1], 1ull);
+}
+
+__global__ __launch_bounds__(256) void join_resolve_kernel(const uint64_t* __restrict__ ks, const uint32_t* __restrict__ vs, int64_t N, int64_t H, const uint64_t* __restrict__ src,
+                                                           const uint32_t* __restrict__ info, ResolveOut o)
+{
+	const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+	for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < N; j += stride)
+	{
+		const uint64_t k = ks[j];
+		if (k == KEY_NONE || (j > 0 && ks[j - 1] == k)) continue;
+		int64_t e = j + 1;
+		while (e < N && ks[e] == k) ++e;
+		const uint8_t* first = (const uint8_t*)(uintptr_t)src[vs[j]];
+		bool same = true;
+		for (int64_t q = j + 1; q < e && same; ++q) same = same_name(first, (const uint8_t*)(uintptr_t)src[vs[q]]);
+		if (same)
+		{
+			int64_t q = j;
+			for (; q + 1 < e; q += 2) close_pair(o, info, H, vs[q], vs[q + 1]);
+			if (q < e) o.held[q] = 1;
+		}
+		else   // a hash collision: pair name by name, in file order
+		{
+			for (int64_t q = j; q < e; ++q)
+			{
+				const uint8_t* a = (const uint8_t*)(uintptr_t)src[vs[q]];
+				int64_t f = -1;
+				for (int64_t r = j; r < q && f < 0; ++r) if (o.st[r] == 1 && same_name((const uint8_t*)(uintptr_t)src[vs[r]], a)) f = r;
+				if (f >= 0) { o.st[f] = 2; o.st[q] = 2; close_pair(o, info, H, vs[f], vs[q]); }
+				else o.st[q] = 1;
+			}
+			for (int64_t q = j; q < e; ++q) o.held[q] = o.st[q] == 1 ? 1 : 0;
+		}
+	}
+}
+
+// the bytes a held entry keeps: the whole record when it passes, else the fixed part and the name (all a later name comparison reads)
+__global__ __launch_bounds__(256) void held_bytes_kernel(const uint8_t* __restrict__ held, const uint32_t* __restrict__ vs, int64_t N, const uint64_t* __restrict__ src, const uint32_t* __restrict__ info, uint64_t* __restrict__ nb)
+{
+	const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+	for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < N; j += stride)
+	{
+		if (!held[j]) { nb[j] = 0; continue; }
+		const uint8_t* s = (const uint8_t*)(uintptr_t)src[vs[j]];
+		nb[j] = (info[vs[j]] >> 31) ? (uint64_t)ld32(s) + 4 : 36ull + s[12];
+	}
+}
+
+__global__ __launch_bounds__(256) void held_store_kernel(const uint8_t* __restrict__ held, const uint64_t* __restrict__ hpos, const uint64_t* __restrict__ nb, const uint64_t* __restrict__ boff,
+                                                         const uint32_t* __restrict__ vs, const uint64_t* __restrict__ ks, int64_t N, const uint64_t* __restrict__ src, const uint32_t* __restrict__ info,
+                                                         uint8_t* __restrict__ pool, uint64_t* __restrict__ hk, uint64_t* __restrict__ hs, uint32_t* __restrict__ hi)
+{
+	const int lane = threadIdx.x & 63;
+	const int64_t nw = ((int64_t)gridDim.x * blockDim.x) >> 6;
+	for (int64_t j = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6; j < N; j += nw)
+	{
+		if (!held[j]) continue;
+		const uint8_t* s = (const uint8_t*)(uintptr_t)src[vs[j]];
+		uint8_t* d = pool + boff[j];
+		for (uint64_t i = lane; i < nb[j]; i += 64) d[i] = s[i];
+		if (lane == 0) { const uint64_t h = hpos[j]; hk[h] = ks[j]; hs[h] = (uint64_t)(uintptr_t)d; hi[h] = info[vs[j]]; }
+	}
+}
+
+unsigned grid_for(int64_t n, int per = 256) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + per - 1) / per, 65536)); }
+
+// compressed members to the file: two pinned buffers, a host thread writes one while the next is filled
+struct FileSink
+{
+	FILE* f = nullptr; std::thread th; std::mutex mu; std::condition_variable cv;
+	PinBuf<uint8_t> pb[2]; size_t len[2] = {0, 0}; bool full[2] = {false, false}; bool stop = false; std::string err; int next = 0;
+	double write_ms = 0;
+	void open(const char* path, const std::string& fail_msg)
+	{
+		f = fopen(path, "wb");
+		if (!f) throw IoError(fail_msg);
+		th = std::thread([this] { run(); });
+	}
+	void run()
+	{
+		int cur = 0;
+		std::unique_lock<std::mutex> lk(mu);
+		for (;;)
+		{
+			cv.wait(lk, [&] { return full[cur] || stop; });
+			if (!full[cur]) return;
+			lk.unlock();
+			const double t0 = wall_ms();
+			const bool ok = fwrite(pb[cur].p, 1, len[cur], f) == len[cur];
+			lk.lock();
+			write_ms += wall_ms() - t0;
+			if (!ok && err.empty()) err = "write error";
+			full[cur] = false; cur ^= 1; cv.notify_all();
+		}
+	}
+	uint8_t* slot(size_t n)   // waits until the next buffer is free
+	{
+		std::unique_lock<std::mutex> lk(mu);
+		cv.wait(lk, [&] { return !full[next]; });
+		lk.unlock();
+		pb[next].ensure(std::max<size_t>(n, 1));
+		return pb[next].p;
+	}
+	void commit(size_t n) { { std::lock_guard<std::mutex> g(mu); len[next] = n; full[next] = true; } cv.notify_all(); next ^= 1; }
+	void put_device(const uint8_t* d, size_t n, hipStream_t s)
+	{
+		if (!n) return;
+		uint8_t* p = slot(n);
+		HIPCHK(hipMemcpyAsync(p, d, n, hipMemcpyDeviceToHost, s)); HIPCHK(hipStreamSynchronize(s));
+		commit(n);
+	}
+	void put_host(const uint8_t* h, size_t n) { if (!n) return; uint8_t* p = slot(n); memcpy(p, h, n); commit(n); }
+	void finish()
+	{
+		{ std::lock_guard<std::mutex> g(mu); stop = true; } cv.notify_all();
+		if (th.joinable()) th.join();
+		if (f) { if (fclose(f) != 0 && err.empty()) err = "close error"; f = nullptr; }
+	}
+	~FileSink() { finish(); }
+};
+
+const uint8_t BGZF_EOF[28] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 0x42, 0x43, 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+
+// device buffers of the join and the held set grow with the tile and with the names still open: planned against hipMemGetInfo before they are allocated
+// device buffers of the join and the held set grow with the tile and with the names still open: planned against hipMemGetInfo before they are allocated
+template <typename T> void grow(DevBuf<T>& b, size_t n, const char* what, const char* tool)
+{
+	if (b.n >= n) return;
+	const size_t want = (n + n / 4 + 1024) * sizeof(T);
+	size_t fr = 0, tot = 0;
+	if (hipMemGetInfo(&fr, &tot) == hipSuccess && want > fr + b.n * sizeof(T))
+	{
+		reaper().drain();   // (memory on its way back to the driver)
+		if (hipMemGetInfo(&fr, &tot) == hipSuccess && want > fr + b.n * sizeof(T))
+			throw std::runtime_error(std::string(tool) + ": " + what + " does not fit in device memory (" + std::to_string(want >> 20) + " MiB needed, " + std::to_string(fr >> 20) + " MiB free)");
+	}
+	try { b.alloc(n + n / 4 + 1024); }
+	catch (std::exception& e) { throw std::runtime_error(std::string(tool) + ": " + what + " does not fit in device memory (" + std::to_string((n * sizeof(T)) >> 20) + " MiB asked for; " + e.what() + ")"); }
+}
+
+// A window of an output stream: the bytes [lo, hi) of obuf are written, a record at position pos (relative to obuf[0]; negative: it began in an earlier window)
+// writes only what falls inside - so a record that straddles two windows is written in two launches, the same bytes each time.
+struct Win { uint8_t* base; int64_t lo, hi; };
+__device__ __forceinline__ void put(const Win& w, int64_t& pos, uint8_t v) { if (pos >= w.lo && pos < w.hi) w.base[pos] = v; ++pos; }
+
+struct NameJoin
+{
+	const char* tool;
+	DevBuf<uint64_t> key, skey, src, nb, boff, hpos, hk, hs; DevBuf<uint32_t> val, sval, info, hi; DevBuf<int64_t> close_of; DevBuf<uint8_t> held, st, tmp, pool[2];
+	DevBuf<unsigned long long> counts;
+	int cur_pool = 0; int64_t H = 0; uint64_t newH = 0;
+	explicit NameJoin(const char* t, hipStream_t s) : tool(t) { counts.alloc(4); HIPCHK(hipMemsetAsync(counts.p, 0, 4 * sizeof(unsigned long long), s)); }
+	// the entry arrays for H + n entries, the held entries in front; tmp also serves the tool's scans of up to H + n uint64 values
+	void begin_tile(int64_t n, hipStream_t s)
+	{
+		const size_t N = (size_t)(H + n);
+		const char* w = "the pair join";
+		grow(key, N + 1, w, tool); grow(skey, N + 1, w, tool); grow(val, N + 1, w, tool); grow(sval, N + 1, w, tool); grow(src, N + 1, w, tool); grow(info, N + 1, w, tool);
+		grow(held, N + 1, w, tool); grow(st, N + 1, w, tool); grow(close_of, (size_t)n + 1, w, tool); grow(nb, N + 1, w, tool); grow(boff, N + 1, w, tool); grow(hpos, N + 1, w, tool);
+		if (H)
+		{
+			HIPCHK(hipMemcpyAsync(key.p, hk.p, (size_t)H * 8, hipMemcpyDeviceToDevice, s)); HIPCHK(hipMemcpyAsync(src.p, hs.p, (size_t)H * 8, hipMemcpyDeviceToDevice, s));
+			HIPCHK(hipMemcpyAsync(info.p, hi.p, (size_t)H * 4, hipMemcpyDeviceToDevice, s));
+		}
+		if (!N) return;
+		// (every temporary size first: a buffer must not be replaced while a queued kernel still uses it)
+		size_t tb = 0, sb1 = 0, sb2 = 0;
+		(void)rocprim::radix_sort_pairs(nullptr, tb, key.p, skey.p, val.p, sval.p, N, 0, 64, s);
+		(void)rocprim::exclusive_scan(nullptr, sb1, nb.p, boff.p, (uint64_t)0, N, rocprim::plus<uint64_t>(), s);
+		(void)rocprim::exclusive_scan(nullptr, sb2, held.p, hpos.p, (uint64_t)0, N, rocprim::plus<uint64_t>(), s);
+		grow(tmp, std::max(tb, std::max(sb1, sb2)) + 16, w, tool);
+	}
+	// after the tool's keys kernel: sort by hash and pair
+	void sort_resolve(int64_t n, hipStream_t s)
+	{
+		const int64_t N = H + n;
+		size_t tb = tmp.n;
+		if (rocprim::radix_sort_pairs(tmp.p, tb, key.p, skey.p, val.p, sval.p, (size_t)N, 0, 64, s) != hipSuccess) throw std::runtime_error("rocprim::radix_sort_pairs failed");
+		if (n) HIPCHK(hipMemsetAsync(close_of.p, 0xff, (size_t)n * sizeof(int64_t), s));
+		HIPCHK(hipMemsetAsync(held.p, 0, (size_t)N, s));
+		hipLaunchKernelGGL(join_resolve_kernel, dim3(grid_for(N)), dim3(256), 0, s, skey.p, sval.p, N, H, src.p, info.p, ResolveOut{close_of.p, held.p, st.p, counts.p}); KCHECK();
+	}
+	// the open entries: their bytes leave the tile buffer into the other pool (the tile buffer is overwritten by K1 later); waits for the stream once
+	void keep_open(int64_t n, hipStream_t s)
+	{
+		const int64_t N = H + n;
+		hipLaunchKernelGGL(held_bytes_kernel, dim3(grid_for(N)), dim3(256), 0, s, held.p, sval.p, N, src.p, info.p, nb.p); KCHECK();
+		uint64_t hcnt[4] = {0, 0, 0, 0};
+		size_t sb = tmp.n;
+		if (rocprim::exclusive_scan(tmp.p, sb, nb.p, boff.p, (uint64_t)0, (size_t)N, rocprim::plus<uint64_t>(), s) != hipSuccess) throw std::runtime_error("rocprim::exclusive_scan failed");
+		sb = tmp.n;
+		if (rocprim::exclusive_scan(tmp.p, sb, held.p, hpos.p, (uint64_t)0, (size_t)N, rocprim::plus<uint64_t>(), s) != hipSuccess) throw std::runtime_error("rocprim::exclusive_scan failed");
+		HIPCHK(hipMemcpyAsync(&hcnt[0], boff.p + N - 1, 8, hipMemcpyDeviceToHost, s)); HIPCHK(hipMemcpyAsync(&hcnt[1], nb.p + N - 1, 8, hipMemcpyDeviceToHost, s));
+		HIPCHK(hipMemcpyAsync(&hcnt[2], hpos.p + N - 1, 8, hipMemcpyDeviceToHost, s));
+		uint8_t last_held = 0; HIPCHK(hipMemcpyAsync(&last_held, held.p + N - 1, 1, hipMemcpyDeviceToHost, s));
+		HIPCHK(hipStreamSynchronize(s));
+		hcnt[3] = last_held;
+		const uint64_t pool_bytes = hcnt[0] + hcnt[1]; newH = hcnt[2] + hcnt[3];
+		DevBuf<uint8_t>& np = pool[cur_pool ^ 1];
+		const char* w = "the open read names (held set)";
+		grow(np, (size_t)pool_bytes + 64, w, tool);
+		// (the held arrays are rewritten: their old contents were copied into the entry arrays in begin_tile)
+		grow(hk, (size_t)newH + 1, w, tool); grow(hs, (size_t)newH + 1, w, tool); grow(hi, (size_t)newH + 1, w, tool);
+		hipLaunchKernelGGL(held_store_kernel, dim3(grid_for(N, 4)), dim3(256), 0, s, held.p, hpos.p, nb.p, boff.p, sval.p, skey.p, N, src.p, info.p, np.p, hk.p, hs.p, hi.p); KCHECK();
+	}
+	// after the stream has passed the last use of the tile's bytes and of the old pool
+	void end_tile() { cur_pool ^= 1; H = (int64_t)newH; }
+	void read_counts(unsigned long long* c, hipStream_t s) { HIPCHK(hipMemcpyAsync(c, counts.p, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s)); HIPCHK(hipStreamSynchronize(s)); }
+};
+
+// one output stream in windows of W bytes (NGSQC_WRITE_WINDOW_PIECES: pieces of 0xff00 bytes per window, a test hook; default about 1 GiB): its device and pinned
+// memory does not depend on the size of the file or of a tile
+inline int64_t write_window_bytes()
+{
+	const char* wp = getenv("NGSQC_WRITE_WINDOW_PIECES");
+	return std::max<int64_t>(1, wp ? atoll(wp) : 16384) * BGZF_PIECE;
+}
+
+struct BgzfStream
+{
+	const char* tool; int64_t W; int level; FileSink sink; BgzfDeflater z;   // (the encoder's slots grow with the largest window deflated, at most W)
+	DevBuf<uint8_t> obuf, zbuf;
+	int64_t carry = 0, ws = 0;   // ws: stream position of obuf[0]; obuf[0, carry) holds the partial piece in front of what comes next
+	double ms_deflate = 0, ms_copy = 0;
+	BgzfStream(const char* t, int64_t w, int lv) : tool(t), W(w), level(lv) {}
+	void deflate_out(int64_t bytes, hipStream_t s, int device)   // the first `bytes` of obuf (whole pieces, or the tail at the end) to the file
+	{
+		if (bytes <= 0) return;
+		const double t0 = wall_ms();
+		grow(zbuf, bgzf_max_bytes(bytes), "the compressed output window", tool);   // (bytes <= W: bounded)
+		const size_t zn = z.run(obuf.p, bytes, zbuf.p, s, device, level);
+		const double t1 = wall_ms(); ms_deflate += t1 - t0;
+		sink.put_device(zbuf.p, zn, s);   // (waits while both pinned buffers are still being written)
+		ms_copy += wall_ms() - t1;
+	}
+	// obuf grows with what a window needs, up to W, keeping the partial piece in front (a small file never allocates a whole window)
+	void ensure_obuf(int64_t need, hipStream_t s)
+	{
+		if ((int64_t)obuf.n >= need) return;
+		DevBuf<uint8_t> nbf; grow(nbf, (size_t)std::min<int64_t>(W, need + need / 4), "the output window", tool);
+		if (nbf.n > (size_t)W) { nbf.release(); nbf.alloc((size_t)W); }
+		if (carry) HIPCHK(hipMemcpyAsync(nbf.p, obuf.p, (size_t)carry, hipMemcpyDeviceToDevice, s));
+		HIPCHK(hipStreamSynchronize(s));
+		std::swap(obuf.p, nbf.p); std::swap(obuf.n, nbf.n);
+	}
+	// the stream up to position out_end, in windows: fill(Win, ws) writes [have, w_end) of a window, whole pieces go to the encoder, the partial piece to the front
+	template <typename F> void emit(int64_t out_end, hipStream_t s, int device, F fill)
+	{
+		for (;;)
+		{
+			const int64_t w_end = std::min<int64_t>(out_end, ws + W), have = ws + carry;
+			if (w_end > have)
+			{
+				ensure_obuf(w_end - ws, s);
+				fill(Win{obuf.p, have - ws, w_end - ws}, ws);
+			}
+			const int64_t fill_n = w_end - ws, whole = fill_n / BGZF_PIECE * BGZF_PIECE;
+			if (whole)
+			{
+				deflate_out(whole, s, device);
+				carry = fill_n - whole;
+				if (carry) HIPCHK(hipMemcpyAsync(obuf.p, obuf.p + whole, (size_t)carry, hipMemcpyDeviceToDevice, s));   // (carry < one piece <= whole: no overlap)
+				ws += whole;
+			}
+			else carry = fill_n;
+			if (w_end >= out_end) break;
+		}
+	}
+	void finish(hipStream_t s, int device) { deflate_out(carry, s, device); carry = 0; sink.put_host(BGZF_EOF, sizeof(BGZF_EOF)); sink.finish(); }
+};
+} // namespace
+} // namespace ngsqc
