@@ -61,22 +61,24 @@ __global__ __launch_bounds__(256) void line_sums_kernel(const int32_t* __restric
 	}
 }
 
-// runs of pred(depth) inside each line; WRITE=false counts runs per line, WRITE=true emits (line,start,end) at base[line]
+// runs of pred(depth) inside each line; WRITE=false counts runs per line, WRITE=true emits (line,start,end) at base[line].
+// n_in: positions of each line up to its contig's end, or null. The sweep keeps a depth array of contig length + 1 and reads 0 behind it
+// (WorkerLowOrHighCoverageChr, oracle/stats.hpp low_high_coverage), so a line's positions behind the contig end have depth 0 there.
 template <bool WRITE>
 __global__ __launch_bounds__(256) void line_runs_kernel(const int32_t* __restrict__ depth, const int64_t* __restrict__ slot, const int32_t* __restrict__ n,
-                                                        const int32_t* __restrict__ line_start, int64_t n_lines, int32_t cutoff, int32_t is_high, int32_t sat,
+                                                        const int32_t* __restrict__ n_in, const int32_t* __restrict__ line_start, int64_t n_lines, int32_t cutoff, int32_t is_high, int32_t sat,
                                                         uint32_t* __restrict__ cnt, const int64_t* __restrict__ base, ngsqc_run* __restrict__ runs)
 {
 	const int lane = threadIdx.x & 63;
 	const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = ((int64_t)gridDim.x * blockDim.x) >> 6;
 	for (int64_t l = wave; l < n_lines; l += n_waves)
 	{
-		const int32_t* d = depth + slot[l]; const int len = n[l];
+		const int32_t* d = depth + slot[l]; const int len = n[l], len_in = n_in ? n_in[l] : len;
 		uint32_t n_start = 0, n_end = 0;
 		for (int j0 = 0; j0 < len; j0 += 64)
 		{
 			int j = j0 + lane;
-			auto pred = [&](int k) -> bool { if (k < 0 || k >= len) return false; int v = d[k]; if (sat && v > 254) v = 254; return is_high ? v >= cutoff : v < cutoff; };
+			auto pred = [&](int k) -> bool { if (k < 0 || k >= len) return false; int v = k < len_in ? d[k] : 0; if (sat && v > 254) v = 254; return is_high ? v >= cutoff : v < cutoff; };
 			bool cur = pred(j), prev = pred(j - 1), next = pred(j + 1);
 			bool is_start = cur && !prev, is_end = cur && !next;
 			unsigned long long ms = __ballot(is_start), me = __ballot(is_end);
@@ -134,14 +136,14 @@ void launch_line_sums(const int32_t* d_depth, const int64_t* d_slot, const int32
 	hipLaunchKernelGGL(line_sums_kernel, dim3(grid), dim3(256), 0, s, d_depth, d_slot, d_n, n_lines, d_sums); KCHECK();
 }
 
-void launch_line_runs(bool write, const int32_t* d_depth, const int64_t* d_slot, const int32_t* d_n, const int32_t* d_line_start, int64_t n_lines,
+void launch_line_runs(bool write, const int32_t* d_depth, const int64_t* d_slot, const int32_t* d_n, const int32_t* d_n_in, const int32_t* d_line_start, int64_t n_lines,
                       int32_t cutoff, int32_t is_high, int32_t sat, uint32_t* d_cnt, const int64_t* d_base, ngsqc_run* d_runs, hipStream_t s)
 {
 	if (n_lines <= 0) return;
 	int64_t wgs = (n_lines + 3) / 4;
 	int grid = (int)(wgs < 2048 ? wgs : 2048);
-	if (write) hipLaunchKernelGGL(line_runs_kernel<true>, dim3(grid), dim3(256), 0, s, d_depth, d_slot, d_n, d_line_start, n_lines, cutoff, is_high, sat, d_cnt, d_base, d_runs);
-	else hipLaunchKernelGGL(line_runs_kernel<false>, dim3(grid), dim3(256), 0, s, d_depth, d_slot, d_n, d_line_start, n_lines, cutoff, is_high, sat, d_cnt, d_base, d_runs);
+	if (write) hipLaunchKernelGGL(line_runs_kernel<true>, dim3(grid), dim3(256), 0, s, d_depth, d_slot, d_n, d_n_in, d_line_start, n_lines, cutoff, is_high, sat, d_cnt, d_base, d_runs);
+	else hipLaunchKernelGGL(line_runs_kernel<false>, dim3(grid), dim3(256), 0, s, d_depth, d_slot, d_n, d_n_in, d_line_start, n_lines, cutoff, is_high, sat, d_cnt, d_base, d_runs);
 	KCHECK();
 }
 

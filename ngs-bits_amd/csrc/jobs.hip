@@ -1125,10 +1125,14 @@ int ngsqc_lowhigh_runs(ngsqc_handle* h, const ngsqc_region* lines, int64_t n_lin
 		DevBuf<int64_t> d_slot; d_slot.upload(slot, h->stream);
 		DevBuf<int32_t> d_len; d_len.upload(len, h->stream);
 		DevBuf<int32_t> d_ls; d_ls.upload(ls, h->stream);
+		// the sweep (saturate254) reads depth 0 behind the contig end: positions of each line up to it
+		std::vector<int32_t> len_in((size_t)n_lines);
+		for (int64_t i = 0; i < n_lines; ++i) len_in[(size_t)i] = (int32_t)std::max<int64_t>(0, std::min<int64_t>(len[(size_t)i], h->ref_lens[(size_t)lines[i].tid] - lines[i].start + 1));
+		DevBuf<int32_t> d_in; if (saturate254) d_in.upload(len_in, h->stream);
 		DevBuf<uint32_t> d_cnt; d_cnt.alloc((size_t)n_lines + 1);
 		DevBuf<int64_t> d_base; d_base.alloc((size_t)n_lines + 1);
 		DevBuf<uint8_t> d_tmp; d_tmp.alloc(scan_tmp_bytes(n_lines) + 64);
-		launch_line_runs(false, D.d_depth.p, d_slot.p, d_len.p, d_ls.p, n_lines, cutoff, is_high, saturate254, d_cnt.p, nullptr, nullptr, h->stream);
+		launch_line_runs(false, D.d_depth.p, d_slot.p, d_len.p, saturate254 ? d_in.p : nullptr, d_ls.p, n_lines, cutoff, is_high, saturate254, d_cnt.p, nullptr, nullptr, h->stream);
 		launch_scan_counts(d_cnt.p, n_lines, d_base.p, d_tmp.p, h->stream);
 		int64_t total = 0;
 		HIPCHK(hipMemcpyAsync(&total, d_base.p + n_lines, sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
@@ -1136,7 +1140,7 @@ int ngsqc_lowhigh_runs(ngsqc_handle* h, const ngsqc_region* lines, int64_t n_lin
 		*n_runs = total;
 		if (!runs || cap < total || total == 0) return;
 		DevBuf<ngsqc_run> d_runs; d_runs.alloc((size_t)total);
-		launch_line_runs(true, D.d_depth.p, d_slot.p, d_len.p, d_ls.p, n_lines, cutoff, is_high, saturate254, d_cnt.p, d_base.p, d_runs.p, h->stream);
+		launch_line_runs(true, D.d_depth.p, d_slot.p, d_len.p, saturate254 ? d_in.p : nullptr, d_ls.p, n_lines, cutoff, is_high, saturate254, d_cnt.p, d_base.p, d_runs.p, h->stream);
 		HIPCHK(hipMemcpyAsync(runs, d_runs.p, (size_t)total * sizeof(ngsqc_run), hipMemcpyDeviceToHost, h->stream));
 		HIPCHK(hipStreamSynchronize(h->stream));
 	});

@@ -93,8 +93,8 @@ __device__ __forceinline__ long long wave_sum(long long v)
 	return v;
 }
 
-// CG:B,I long CIGAR (htslib bam_tag2cigar): behind a first operation kS with k == l_seq, the tag's array replaces the CIGAR when it holds at least n_cigar
-// operations. rec_cg_tag looks the tag up (the caller has checked the first operation): the array, or null; rec_apply_cg does both for one record
+// CG:B,I long CIGAR (htslib bam_tag2cigar): on a placed record (tid >= 0 and pos >= 0), behind a first operation kS with k == l_seq, the tag's array replaces the
+// CIGAR when it holds at least n_cigar operations (the oracle's parse_rec, oracle/bamio.hpp). rec_cg_tag looks the tag up (the caller has checked the first operation): the array, or null; rec_apply_cg does both for one record
 __device__ __forceinline__ const uint8_t* rec_cg_tag(const RecView& r, uint32_t& n)
 {
 	const uint8_t* t = aux_find(rec_aux(r), rec_end(r), 'C', 'G');
@@ -103,7 +103,7 @@ __device__ __forceinline__ const uint8_t* rec_cg_tag(const RecView& r, uint32_t&
 }
 __device__ __forceinline__ void rec_apply_cg(RecView& r)
 {
-	if (r.n_cigar_raw == 0 || r.pos < 0) return;
+	if (r.n_cigar_raw == 0 || r.tid < 0 || r.pos < 0) return;
 	const uint32_t c0 = ld32(r.cigar);
 	if ((c0 & 15u) != 4 || (int32_t)(c0 >> 4) != r.l_seq) return;
 	uint32_t n = 0; const uint8_t* cg = rec_cg_tag(r, n);

@@ -1161,7 +1161,7 @@ __global__ __launch_bounds__(256) void pileup_long_kernel(const uint8_t* __restr
 	for (long long w = wave; w < n_long; w += n_waves)
 	{
 		RecView r = load_rec(infl, recoff[long_list[w]]);      // (passed the read filters in pileup_kernel)
-		if (r.n_cigar_raw > 0 && r.pos >= 0)
+		if (r.n_cigar_raw > 0 && r.tid >= 0 && r.pos >= 0)
 		{
 			const uint32_t c0 = ld32(r.cigar);
 			if ((c0 & 15u) == 4 && (int32_t)(c0 >> 4) == r.l_seq)

@@ -54,6 +54,15 @@ int64_t orc_bam_record_offsets(void* b, int64_t* out, int64_t cap)
 	for (int64_t i=0;i<n;++i) out[i] = (int64_t)f->rec_off[i];
 	return n;
 }
+// the effective CIGAR of record i as parse_rec leaves it (the CG:B,I rule applied): returns the number of operations, copies up to cap of them
+int64_t orc_bam_effective_cigar(void* b, int64_t i, uint32_t* out, int64_t cap)
+{
+	auto* f = (BamFile*)b;
+	if (i < 0 || (size_t)i >= f->rec_off.size()) return -1;
+	Rec r = f->rec((size_t)i);
+	for (int64_t k=0; k<std::min<int64_t>(cap, (int64_t)r.n_cigar); ++k) out[k] = rd32(r.cigar_raw + 4*k);
+	return (int64_t)r.n_cigar;
+}
 
 // mode: 0 = Statistics::mapping(bed,...) [ROI], 1 = Statistics::mapping(bam,...) [no ROI], 2 = Statistics::mapping_wgs
 // bed: path or NULL ; merge_bed: apply BedFile::merge() after load (MappingQC main.cpp:130-132) ; fasta: path or NULL

@@ -64,8 +64,8 @@ class Rec:
         return 0
 
     def cg(self):
-        """(ops, tag start, tag end) when the CIGAR comes from the CG tag (htslib bam_tag2cigar, as rec_apply_cg), else None"""
-        if not self.cigar or self.pos < 0:
+        """(ops, tag start, tag end) when the CIGAR comes from the CG tag (htslib bam_tag2cigar, as the oracle's parse_rec: a placed record, tid >= 0 and pos >= 0), else None"""
+        if not self.cigar or self.tid < 0 or self.pos < 0:
             return None
         if self.cigar[0] & 15 != 4 or self.cigar[0] >> 4 != self.l_seq:
             return None

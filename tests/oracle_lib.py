@@ -42,6 +42,7 @@ def lib():
         L.orc_bam_ref_len.restype = i64; L.orc_bam_ref_len.argtypes = [vp, i32]
         L.orc_bam_inflated.restype = i64; L.orc_bam_inflated.argtypes = [vp, vp, i64]
         L.orc_bam_record_offsets.restype = i64; L.orc_bam_record_offsets.argtypes = [vp, vp, i64]
+        L.orc_bam_effective_cigar.restype = i64; L.orc_bam_effective_cigar.argtypes = [vp, i64, vp, i64]
         L.orc_mapping.restype = vp; L.orc_mapping.argtypes = [vp, i32, cp, i32, cp, i32, i32, cp, i32]
         L.orc_result_counters.argtypes = [vp, vp]
         L.orc_result_text.restype = cp; L.orc_result_text.argtypes = [vp]
@@ -102,6 +103,15 @@ class Bam:
         a = np.empty(self.count, dtype=np.int64)
         lib().orc_bam_record_offsets(self.h, a.ctypes.data, a.size)
         return a
+
+    def effective_cigar(self, i):
+        """the CIGAR of record i as the oracle reads it (parse_rec: a CG:B,I tag applied), as raw u32 words"""
+        n = lib().orc_bam_effective_cigar(self.h, i, None, 0)
+        if n < 0:
+            raise IndexError(i)
+        a = np.zeros(max(n, 1), dtype=np.uint32)
+        lib().orc_bam_effective_cigar(self.h, i, a.ctypes.data, n)
+        return [int(x) for x in a[:n]]
 
 
 class MappingResult:

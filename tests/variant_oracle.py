@@ -26,8 +26,8 @@ def _i32(a, o):
     return v - (1 << 32) if v >= 1 << 31 else v
 
 
-def _cg_tag(img, aux, end):
-    """the payload of a CG:B,I tag (htslib bam_tag2cigar), or None"""
+def _cg_tag(img, aux, end, n_cig):
+    """the payload of a CG:B,I tag with n_cig <= n < 2^29 entries (htslib bam_tag2cigar, the oracle's parse_rec), or None"""
     p = aux
     sizes = {ord("A"): 1, ord("c"): 1, ord("C"): 1, ord("s"): 2, ord("S"): 2, ord("i"): 4, ord("I"): 4, ord("f"): 4, ord("d"): 8}
     while p + 3 <= end:
@@ -35,6 +35,8 @@ def _cg_tag(img, aux, end):
         if tag == b"CG":
             if t == ord("B") and int(img[p + 3]) == ord("I"):
                 n = _u32(img, p + 4)
+                if n < n_cig or n >= 1 << 29:
+                    return None
                 return [(_u32(img, p + 8 + 4 * k) & 15, _u32(img, p + 8 + 4 * k) >> 4) for k in range(n)]
             return None
         if t in sizes:
@@ -65,9 +67,9 @@ def reads(bam):
         c0 = o + 36 + l_name
         cigar = [(_u32(img, c0 + 4 * k) & 15, _u32(img, c0 + 4 * k) >> 4) for k in range(n_cig)]
         seq_off = c0 + 4 * n_cig
-        if n_cig and pos >= 0 and cigar[0] == (4, l_seq):
-            cg = _cg_tag(img, seq_off + (l_seq + 1) // 2 + l_seq, o + 4 + bs)
-            if cg is not None and len(cg) >= n_cig:
+        if n_cig and tid >= 0 and pos >= 0 and cigar[0] == (4, l_seq):
+            cg = _cg_tag(img, seq_off + (l_seq + 1) // 2 + l_seq, o + 4 + bs, n_cig)
+            if cg is not None:
                 cigar = cg
         r = Read()
         rlen = 0 if flag & 0x4 else sum(n for op, n in cigar if op in REF_OPS)
