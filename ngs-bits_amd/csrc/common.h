@@ -10,6 +10,7 @@
 #include <vector>
 #include "../../include/ngsqc.h"
 #include "k1_types.h"
+#include "cram_plan.h"
 
 namespace ngsqc {
 
@@ -63,16 +64,7 @@ int cram_set_skip_thread(int flags);   // the calling thread's own choice (-1: n
 void cram_set_skip(int flags);   // bit 0: read names, bit 1: optional fields are not needed (not decoded where their blocks are theirs alone)
 int cram_skip();
 struct CramSelect { struct Region { std::string chr; int32_t start, end; }; std::vector<Region> regions; int64_t max_slices = 0; };   // regions: only slices that can hold their records; max_slices: the first slices only
-// The quality arrays of a CRAM (QS series: one rANS 4x8 block per slice, about half of a BAM record's bytes) can stay compressed on the host: the plan names every such
-// block (where its four rANS states start in the CRAM image, its frequency tables in a compact form) and, per record, where its qualities go in the BAM stream; the
-// device decodes the blocks and writes the qualities into the uploaded image (cram_dev.hip).
-struct CramQualPlan
-{
-	struct Job { uint64_t in_off; uint64_t out_off; uint32_t in_len, n_out, tab_off, sym_off; uint32_t order, nsym; };   // in_off: the states + byte stream in the CRAM image; out_off: into the decoded quality bytes of all jobs
-	struct Patch { uint64_t dst, src; uint32_t len, pad; };                                                       // dst: offset in the BAM stream; src: offset in the decoded quality bytes
-	std::vector<Job> jobs; std::vector<uint16_t> tabs; std::vector<uint8_t> syms; std::vector<Patch> patches; uint64_t out_bytes = 0;
-	// tabs: per job (order 0: one row; order 1: nsym rows, row = index of the previous symbol) of nsym + 1 cumulative frequencies; syms: per job 64 symbols + 256 bytes "byte -> index"
-};
+// the plan of the quality blocks that stay compressed on the host and are decoded on the device: cram_plan.h
 // a byte buffer that is NOT zeroed when it is made (a BAM image of a WGS CRAM is ~100 GB: the workers that fill it touch its pages, in parallel)
 struct ByteImage
 {

@@ -21,12 +21,15 @@ K1_DEV u32x4 make4(uint32_t a, uint32_t b, uint32_t c, uint32_t d) { return make
 K1_DEV int lane() { return (int)(threadIdx.x & 63u); }
 K1_DEV int64_t block_id() { return (int64_t)blockIdx.x; }
 K1_DEV int64_t grid_size() { return (int64_t)gridDim.x; }
+K1_DEV uint32_t thread_id() { return threadIdx.x; }   // inside the workgroup (a workgroup of more than one wave: cram_patch_kernel)
+K1_DEV uint32_t block_dim() { return blockDim.x; }
 
 // ---- cross-lane (call in wave-uniform control flow only) ----
 K1_DEV uint64_t ballot(bool p) { return __builtin_amdgcn_ballot_w64(p); }
 K1_DEV uint32_t readlane(uint32_t v, int l) { return (uint32_t)__builtin_amdgcn_readlane((int)v, l); }
 K1_DEV uint32_t shfl(uint32_t v, int src) { return (uint32_t)__builtin_amdgcn_ds_bpermute(src << 2, (int)v); }
 K1_DEV void barrier() { __builtin_amdgcn_wave_barrier(); }   // orders LDS traffic between the lanes of the wave (a compiler fence: the wave runs in lockstep)
+K1_DEV void wg_barrier() { __syncthreads(); }   // the WORKGROUP barrier, with the wait for the LDS traffic in front of it (what barrier() above is not)
 // inclusive prefix sum on the DPP network: Hillis-Steele inside each 16-lane row (row_shr:1/2/4/8, out-of-row sources read 0),
 // then row_bcast:15 into rows 1 and 3 and row_bcast:31 into rows 2-3
 K1_DEV uint32_t scan_incl(uint32_t x)
@@ -45,6 +48,7 @@ K1_DEV void wait_vm0() { __builtin_amdgcn_s_waitcnt(0x0F70); }
 K1_DEV void wait_vm4() { __builtin_amdgcn_s_waitcnt(0x0F74); }   // vmcnt(4): all but the last four vector-memory operations are done (loads return in order)   // vmcnt(0): every vector-memory load has returned, every store is acknowledged
 K1_DEV unsigned long long atomic_inc(unsigned long long* p) { return atomicAdd(p, 1ull); }
 K1_DEV uint32_t atomic_add_u32(uint32_t* p, uint32_t v) { return atomicAdd(p, v); }
+K1_DEV void atomic_or_u32(unsigned int* p, unsigned int v) { atomicOr(p, v); }   // a word in global memory
 K1_DEV void lds_or(unsigned long long* p, unsigned long long v) { atomicOr(p, v); }
 K1_DEV void lds_or32(uint32_t* p, uint32_t v) { atomicOr(p, v); }
 // a dword of LDS at any byte address (gfx950 runs with unaligned access mode: one ds_read_b32) / at a 4-aligned one

@@ -445,12 +445,15 @@ def huffman_lengths(values):
     return syms, [depth[s] for s in syms]
 
 
+QS_SHARED_BLOCK = False   # test switch: the BA series (bases of unmapped reads, 'B' / 'i' features) shares the external block of the qualities
 SHARED_BLOCK = False   # test switch: RN, IN and the first tag's values share one external block (the skip bookkeeping of the product must keep all of them: tests/test_cpu_cram.py)
 
 
-def encode(bam_path, out_path, genome=None, slice_records=2500, rr=True, multi_ref=False, chains=True, embed_ref=False, variety=True, methods=None, qual_features=False, slices_per_container=1, version=(3, 0), name_method=None):
+def encode(bam_path, out_path, genome=None, slice_records=2500, rr=True, multi_ref=False, chains=True, embed_ref=False, variety=True, methods=None, qual_features=False, slices_per_container=1, version=(3, 0), name_method=None, qs_method=None):
     """genome: {contig name: bytes, upper case}. rr = False writes every base into the file ('b' features: no genome needed to read it). multi_ref packs several
-    references into one slice (RI series, absolute positions). embed_ref stores the slice's reference stretch in the file. variety = False: raw EXTERNAL only."""
+    references into one slice (RI series, absolute positions). embed_ref stores the slice's reference stretch in the file. variety = False: raw EXTERNAL only.
+    slice_records: a number, or a list with the record count of every slice. qs_method: the block method of the quality block (4 = rANS order 0, 41 = rANS order 1,
+    any other method of block()) - one for the file or a list that the slices cycle through; None: order 1 where `variety` picks the methods, else theirs."""
     global NAME_METHOD
     NAME_METHOD = name_method
     text, refs, recs = read_bam(bam_path)
@@ -462,13 +465,15 @@ def encode(bam_path, out_path, genome=None, slice_records=2500, rr=True, multi_r
     groups = []; cur = []
     for r in recs:
         key = r["ref_id"]
-        if cur and ((not multi_ref and key != cur[0]["ref_id"]) or len(cur) >= slice_records): groups.append(cur); cur = []
+        limit = slice_records[len(groups) % len(slice_records)] if isinstance(slice_records, (list, tuple)) else slice_records
+        if cur and ((not multi_ref and key != cur[0]["ref_id"]) or len(cur) >= limit): groups.append(cur); cur = []
         cur.append(r)
     if cur: groups.append(cur)
     counter = 0; crai = []
     for k in range(0, len(groups), max(1, slices_per_container)):
         gs = groups[k:k + max(1, slices_per_container)]; at = len(out)
-        c, line = encode_container(gs, refs, rgs, genome, rr, multi_ref, chains, embed_ref, variety, counter, methods, qual_features); counter += sum(len(g) for g in gs)
+        qs = None if qs_method is None else [(qs_method[(k + i) % len(qs_method)] if isinstance(qs_method, (list, tuple)) else qs_method) for i in range(len(gs))]
+        c, line = encode_container(gs, refs, rgs, genome, rr, multi_ref, chains, embed_ref, variety, counter, methods, qual_features, qs); counter += sum(len(g) for g in gs)
         out += c; crai.append("%d\t%d\t%d\t%d\t%d\t%d\n" % (line[0], line[1], line[2], at, line[3], line[4]))   # (the container's first slice)
     out += eof_container()
     open(out_path, "wb").write(bytes(out))
@@ -481,8 +486,9 @@ def encode_slice(g, refs, rgs, genome, rr, multi_ref, chains, embed_ref, variety
     return encode_container([g], refs, rgs, genome, rr, multi_ref, chains, embed_ref, variety, counter, block_methods, qual_features)
 
 
-def encode_container(gs, refs, rgs, genome, rr, multi_ref, chains, embed_ref, variety, counter, block_methods=None, qual_features=False):
-    """one container of len(gs) slices: ONE compression header (preservation map, encodings, tag dictionary) for all of them, a landmark per slice"""
+def encode_container(gs, refs, rgs, genome, rr, multi_ref, chains, embed_ref, variety, counter, block_methods=None, qual_features=False, qs_methods=None):
+    """one container of len(gs) slices: ONE compression header (preservation map, encodings, tag dictionary) for all of them, a landmark per slice
+    (qs_methods: per slice the method of its quality block, see encode)"""
     # ---- per slice: reference, span, read groups, mate chains, CRAM flags ----
     P = []
     for g in gs:
@@ -522,6 +528,7 @@ def encode_container(gs, refs, rgs, genome, rr, multi_ref, chains, embed_ref, va
         ids.setdefault(key, len(ids) + 1); return ("EXTERNAL", ids[key])
     E = {k: ext(k) for k in ("BF", "RL", "AP", "NP", "TS", "NF", "TL", "FP", "BS", "BA", "QS", "RI", "MF", "NS", "HC", "PD", "RS", "FC")}
     E["RN"] = ("BYTE_ARRAY_STOP", 0, ext("RN")[1]); E["IN"] = ("BYTE_ARRAY_STOP", 0, ext("IN")[1]); E["SC"] = ("BYTE_ARRAY_STOP", 0, ext("SC")[1])
+    if QS_SHARED_BLOCK: E["BA"] = ext("QS")   # (the bases of unmapped reads and the qualities in ONE external block: a reader may not take that block for qualities alone)
     if SHARED_BLOCK: E["RN"] = ("BYTE_ARRAY_STOP", 0, ext("IN")[1])   # (a legal layout htslib does not write: read names, inserted bases and - below - one tag's values in ONE external block)
     E["BB"] = ("BYTE_ARRAY_LEN", ext("BBl"), ext("BBv")); E["QQ"] = ("BYTE_ARRAY_LEN", ext("QQl"), ext("QQv"))
     all_rg = [x for p in P for x in p["rg_of"]]; all_cf = [x for p in P for x in p["cf"]]
@@ -563,7 +570,7 @@ def encode_container(gs, refs, rgs, genome, rr, multi_ref, chains, embed_ref, va
     ch_block = block(0, 1, 0, ch)
     blocks = [ch_block]; landmarks = []; total_bases = 0; at = len(ch_block); first_slice_size = 0; rec_counter = counter
     # ---- slices ----
-    for p in P:
+    for si, p in enumerate(P):
         g, slice_ref, start, span, rg_of, link, cf, tl_of = p["g"], p["ref"], p["start"], p["span"], p["rg_of"], p["link"], p["cf"], p["tl_of"]
         W = SliceWriter(E); prev = start; bases = 0
         embedded = None
@@ -635,6 +642,7 @@ def encode_container(gs, refs, rgs, genome, rr, multi_ref, chains, embed_ref, va
         for k, (cid, data) in enumerate(sorted(W.ext.items())):
             m = methods[k % len(methods)]
             if cid == ids.get("QS") and variety and not block_methods: m = 41
+            if cid == ids.get("QS") and qs_methods is not None: m = qs_methods[si]
             if m in (4, 41) and len(data) > 400000: m = 1
             if NAME_METHOD is not None and cid == ids.get("RN"): m = NAME_METHOD
             ext_blocks.append(block(m, 4, cid, bytes(data))); content_ids.append(cid)

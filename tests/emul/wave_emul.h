@@ -105,6 +105,8 @@ __attribute__((noinline)) inline Xchg rendezvous(uint64_t v, const void* site)
 inline int lane() { return emu().cur; }
 inline int64_t block_id() { return emu().block; }
 inline int64_t grid_size() { return emu().grid; }
+inline uint32_t thread_id() { return (uint32_t)emu().cur; }   // (a workgroup is one wave here: kernels without cross-lane traffic do not notice)
+inline uint32_t block_dim() { return (uint32_t)Emu::W; }
 
 __attribute__((noinline)) inline uint64_t ballot(bool p, int line = __builtin_LINE())
 {
@@ -115,6 +117,7 @@ __attribute__((noinline)) inline uint64_t ballot(bool p, int line = __builtin_LI
 __attribute__((noinline)) inline uint32_t readlane(uint32_t v, int l, int line = __builtin_LINE()) { const Xchg x = rendezvous(v, WV_SITE); return x.has(l & 63) ? (uint32_t)x.v[l & 63] : 0u; }
 __attribute__((noinline)) inline uint32_t shfl(uint32_t v, int src, int line = __builtin_LINE()) { const Xchg x = rendezvous(v, WV_SITE); return x.has(src & 63) ? (uint32_t)x.v[src & 63] : 0u; }
 __attribute__((noinline)) inline void barrier(int line = __builtin_LINE()) { rendezvous(0, WV_SITE); }
+__attribute__((noinline)) inline void wg_barrier(int line = __builtin_LINE()) { rendezvous(0, WV_SITE); }   // (the workgroup is this wave)
 __attribute__((noinline)) inline uint32_t scan_incl(uint32_t v, int line = __builtin_LINE())
 {
 	const Xchg x = rendezvous(v, WV_SITE); const int me = emu().cur; uint32_t s = 0;
@@ -127,6 +130,7 @@ inline void wait_vm4() {}
 inline void set_priority(int) {}
 inline unsigned long long atomic_inc(unsigned long long* p) { return (*p)++; }
 inline uint32_t atomic_add_u32(uint32_t* p, uint32_t v) { const uint32_t o = *p; *p = o + v; return o; }
+inline void atomic_or_u32(unsigned int* p, unsigned int v) { *p |= v; }
 inline void lds_or(unsigned long long* p, unsigned long long v) { *p |= v; }
 inline void lds_or32(uint32_t* p, uint32_t v) { *p |= v; }
 inline uint32_t lds_load32u(const uint8_t* p) { uint32_t v; memcpy(&v, p, 4); return v; }

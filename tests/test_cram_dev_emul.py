@@ -1,0 +1,270 @@
+"""The two CRAM quality kernels (ngs-bits_amd/csrc/cram_dev_kernels.h: the text libngsqc_hip.so compiles for gfx950) under the wave emulator of tests/emul on the
+CPU. Plans come from the product's own rans_plan (ngsqc.cram_to_bam with NGSQC_CRAM_PLAN_DUMP); every job is held against a sequential decoder of the same plan
+(tests/cram_plan_ref.py), against oracle/cram_decode.py rans_decode on the original block (blocks of up to 50 000 bytes: the time budget) and against the qualities the file was written from; the patched stream
+against the host-only path. Inputs: tests/qualgen.py - one crafted quality distribution per slice. Every case must be DECIDED as intended (the plan holds exactly
+the slices the gates of cram.hip let through: 2048 bytes, 64 symbols counting context 0 in order 1, a block that serves QS alone, no lossy-quality record) and must
+REACH the shape it is named for (REACHED below: computed with the sequential reference alone). Damaged plans run here only - on a GPU they are neither reachable
+from a file nor something to provoke. No GPU needed; the GPU runs of the same kernels are tests/test_gpu_cram_quals.py / test_gpu_cram.py."""
+import ctypes as C
+import os
+import random
+import struct
+import subprocess
+import sys
+
+import pytest
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+EMUL = os.path.join(HERE, "emul")
+CSRC = os.path.join(os.path.dirname(HERE), "ngs-bits_amd", "csrc")
+GI = os.path.join(HERE, "golden", "ref_in")
+ngsqc = __import__("importlib").import_module("ngs-bits_amd")
+sys.path.insert(0, os.path.join(os.path.dirname(HERE), "oracle"))
+import cram_decode as CD  # noqa: E402
+import cram_encode as CE  # noqa: E402
+import cram_plan_ref as R  # noqa: E402
+import qualgen  # noqa: E402
+from test_cpu_cram import bam_stream  # noqa: E402
+
+EMU_PAGE_FAULT, EMU_GUARD_WRITTEN, EMU_PLACEMENTS_DIFFER, EMU_NO_MEMORY = 1, 2, 4, 8
+
+
+@pytest.fixture(scope="module")
+def emul():
+    so = os.path.join(EMUL, "libcramemul.so")
+    srcs = [os.path.join(EMUL, "cram_emul.cpp"), os.path.join(EMUL, "wave_emul.h"), os.path.join(CSRC, "cram_dev_kernels.h"), os.path.join(CSRC, "cram_plan.h")]
+    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
+        subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-Wall", "-Wno-unknown-pragmas", "-o", so, srcs[0]])
+    L = C.CDLL(so)
+    L.cram_emul_run.restype = C.c_int
+    L.cram_emul_run.argtypes = [C.c_char_p, C.c_int64, C.c_char_p, C.c_int64, C.c_char_p, C.c_int64, C.c_char_p, C.c_int64, C.c_uint64, C.c_char_p, C.c_uint64,
+                                C.c_char_p, C.c_uint64, C.c_char_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    return L
+
+
+def run(L, plan, cram, stream, decoded=None):
+    """both kernels over the plan -> (decoded quality bytes, per job (status, emulator findings), patched stream, (status, findings) of the patch kernel);
+    decoded: the quality bytes for a plan without jobs (the second kernel alone)"""
+    jobs = b"".join(R.JOB.pack(*j) for j in plan.jobs); tabs = struct.pack("<%dH" % len(plan.tabs), *plan.tabs); patches = b"".join(R.PATCH.pack(*p) for p in plan.patches)
+    n = len(plan.jobs); qs = C.create_string_buffer(decoded, max(1, plan.out_bytes)) if decoded else C.create_string_buffer(max(1, plan.out_bytes)); st = (C.c_uint32 * max(1, n))(); em = (C.c_uint32 * max(1, n))()
+    out = C.create_string_buffer(bytes(stream), max(1, len(stream))); pst = C.c_uint32(0); pem = C.c_uint32(0)
+    rc = L.cram_emul_run(jobs, n, tabs, len(plan.tabs), bytes(plan.syms), len(plan.syms), patches, len(plan.patches), plan.out_bytes, bytes(cram), len(cram),
+                         out, len(stream), qs, st, em, C.byref(pst), C.byref(pem))
+    assert rc == 0
+    return qs.raw[:plan.out_bytes], [(st[i], em[i]) for i in range(n)], out.raw[:len(stream)], (pst.value, pem.value)
+
+
+def product(cram, tmp, monkeypatch):
+    """the product's host-only stream, its blank stream and its plan"""
+    full = os.path.join(tmp, "full.bam"); blank = os.path.join(tmp, "blank.bam"); plan = os.path.join(tmp, "plan.bin")
+    ngsqc.set_reference(None); monkeypatch.setenv("NGSQC_CRAM_NO_REFERENCE", "1"); monkeypatch.delenv("NGSQC_CRAM_PLAN_DUMP", raising=False)
+    ngsqc.cram_to_bam(cram, full)
+    monkeypatch.setenv("NGSQC_CRAM_PLAN_DUMP", plan)
+    try: ngsqc.cram_to_bam(cram, blank)
+    finally: monkeypatch.delenv("NGSQC_CRAM_PLAN_DUMP")
+    return bam_stream(full)[0], bam_stream(blank)[0], R.load_plan(plan)
+
+
+def rans_block_of(cram, job):
+    """the rANS block a job was planned from (order, compressed size, decoded size, tables, states, bytes): the job's stream is its tail"""
+    in_off, _, in_len, n_out, _, _, order, _ = job; end = in_off + in_len
+    for s in range(in_off - 10, max(0, in_off - 70000), -1):
+        if cram[s] == order and struct.unpack_from("<II", cram, s + 1) == (end - s - 9, n_out): return cram[s:end]
+    raise AssertionError("block of the job not found")
+
+
+def check_file(L, made, tmp, monkeypatch):
+    """every assertion the valid cases share -> (plan, per job facts of the sequential reference, {slice name: facts})"""
+    cram = open(made["cram"], "rb").read(); slices = made["slices"]
+    want, blank, plan = product(made["cram"], tmp, monkeypatch)
+    dev = [s for s in slices if s.expect_device()]
+    # decided as intended: the plan holds the slices the gates let through, in file order - and a slice stays on the host only under the name of its gate
+    assert [(j[3], j[6]) for j in plan.jobs] == [(len(s.quals()), 1 if s.qs_method == 41 else 0) for s in dev], "the plan's jobs are not the slices the gates let through"
+    for s in slices: assert s.expect_device() == (s.gate is None), "%s: on the %s, named for %s" % (s.name, "device" if s.expect_device() else "host", s.gate)
+    ref = R.decode_jobs(plan, cram)
+    qs, jst, got, pst = run(L, plan, cram, blank)
+    facts = {}
+    for k, (job, s, (rst, rdata, f)) in enumerate(zip(plan.jobs, dev, ref)):
+        mine = qs[job[1]:job[1] + job[3]]
+        assert jst[k] == (0, 0), "%s: kernel status %d, emulator findings %d" % (s.name, jst[k][0], jst[k][1])
+        assert rst == 0 and mine == rdata, "%s: differs from the sequential reference" % s.name
+        assert mine == s.quals(), "%s: differs from the qualities the file was written from" % s.name
+        if job[3] <= 50000: assert mine == CD.rans_decode(rans_block_of(cram, job)), "%s: differs from rans_decode" % s.name
+        f["nsym"] = job[7]; f["n_out"] = job[3]; f["order"] = job[6]; f["first"] = [rdata[j * (job[3] >> 2)] for j in range(4)]; facts[s.name] = f
+    assert pst == (0, 0)
+    assert got == want, "the patched stream differs from the host-only path"
+    rst, rstream = R.patch_stream(plan, qs, blank)
+    assert rst == 0 and rstream == want
+    assert len(plan.patches) == sum(1 for s in dev for n, q in s.records if n and q is not None)     # no patch for a read without an array
+    return plan, facts, (cram, blank, want)
+
+
+# ---- what each generated case must have exercised: name -> predicate over the sequential reference's facts of that job ----
+REACHED = {
+    "size 2048": lambda f: f["n_out"] == 2048, "size 2049": lambda f: f["n_out"] % 4 == 1, "size 2050": lambda f: f["n_out"] % 4 == 2, "size 2051": lambda f: f["n_out"] % 4 == 3,
+    "size 3000": lambda f: f["n_out"] % 4 == 0, "size 3001": lambda f: f["n_out"] % 4 == 1, "size 3002": lambda f: f["n_out"] % 4 == 2, "size 3003": lambda f: f["n_out"] % 4 == 3,
+    "size 4093": lambda f: f["n_out"] % 4 == 1, "size 4094": lambda f: f["n_out"] % 4 == 2, "size 4095": lambda f: f["n_out"] % 4 == 3, "size 4096": lambda f: f["n_out"] % 4 == 0,
+    "alphabet 1 without quality 0": lambda f: f["nsym"] == 1 + f["order"], "alphabet 2 without quality 0": lambda f: f["nsym"] == 2 + f["order"],
+    "alphabet 3 without quality 0": lambda f: f["nsym"] == 3 + f["order"], "alphabet 63 without quality 0": lambda f: f["nsym"] == 63 + f["order"],
+    "alphabet 64 without quality 0": lambda f: f["nsym"] == 64 and f["order"] == 0, "alphabet 64 with quality 0": lambda f: f["nsym"] == 64,
+    "quality 0 occurs": lambda f: f["nsym"] == 41, "binned 4": lambda f: f["nsym"] == 4 + f["order"], "binned 8": lambda f: f["nsym"] == 8 + f["order"],
+    "above 64": lambda f: f["nsym"] == 60 + f["order"],
+    "single symbol": lambda f: f["min_f"] == 4096 or (f["order"] == 1 and f["max_f"] == 4096),
+    "frequency 1 next to 4088": lambda f: f["min_f"] == 1 and f["max_f"] >= 4088 and f["two"] >= 1 and f["max_two"] == 1,
+    "rare quads": lambda f: f["min_f"] == 1 and f["max_two"] == 4 and f["max_f"] >= 4000,
+    "one successor, never a context": lambda f: f["zero_row"] and f["one_successor"] and len(set(f["first"])) == 4,
+}
+
+
+def test_quality_distributions(emul, tmp_path, monkeypatch):
+    """sizes around the gate and of every residue mod 4, alphabets of 1 .. 65 symbols, binned / uniform / high qualities, frequencies 1 and 4095, two renormalisation
+    bytes in one and in all four states of a round, order-1 contexts with one successor and symbols that are never a context - each in both orders"""
+    slices = qualgen.shapes(); made = qualgen.write(slices, str(tmp_path), "shapes")
+    plan, facts, _ = check_file(emul, made, str(tmp_path), monkeypatch)
+    missed = []
+    for s in slices:
+        case = s.name.rsplit("/", 1)[0]
+        if s.gate is not None: continue
+        assert case in REACHED, case
+        if not REACHED[case](facts[s.name]): missed.append((s.name, {k: v for k, v in facts[s.name].items()}))
+    assert not missed, "cases that did not reach the shape they are named for: %r" % missed
+    # the gates from both sides: 2047 / 2048 bytes, 64 / 65 symbols (order 1: 63 / 64 qualities besides context 0), in both orders
+    on_host = sorted(s.name for s in slices if not s.expect_device())
+    assert on_host == sorted(["size 2047/order0", "size 2047/order1", "alphabet 65 without quality 0/order0", "alphabet 65 without quality 0/order1",
+                              "alphabet 64 without quality 0/order1", "alphabet 65 with quality 0/order0", "alphabet 65 with quality 0/order1"])
+    assert any(f["order"] == 0 for f in facts.values()) and any(f["order"] == 1 for f in facts.values())
+    assert all(len(set(f["first"])) == 4 for n, f in facts.items() if n.startswith("size "))       # sK0 and the four start contexts matter
+
+
+def test_records_against_the_payload_boundaries(emul, tmp_path, monkeypatch):
+    """reads of 0, 1, 2 bases, reads without a quality array between reads with one, a read of 100 000 bases over two payload boundaries in a block of a few hundred
+    KB, the first read of the file ending with a payload, a read starting with one, the last read ending with the stream; three slices per container"""
+    slices = qualgen.record_shapes(); made = qualgen.write(slices, str(tmp_path), "records", slices_per_container=3)
+    plan, facts, (cram, blank, want) = check_file(emul, made, str(tmp_path), monkeypatch)
+    P = plan.patches; P65 = qualgen.PAYLOAD
+    assert len(plan.jobs) == len(slices)
+    crossings = [(d + n - 1) // P65 - d // P65 for d, _, n, _ in P]
+    reached = {
+        "first read ends with a payload": (P[0][0] + P[0][2]) == P65,
+        "last read ends with the stream": (P[-1][0] + P[-1][2]) == len(want) and len(want) % P65 == 0,
+        "a read starts with a payload": any(d % P65 == 0 for d, _, n, _ in P),
+        "a read over two boundaries": max(crossings) >= 2, "a read over one boundary": 1 in crossings,
+        "a read of 100 000 bases": max(n for _, _, n, _ in P) >= 100000,
+        "reads of 1 and 2 bases": {1, 2} <= {n for _, _, n, _ in P},
+        "a block of 170 KB or more": max(j[3] for j in plan.jobs) >= 170000,        # (the issue's "few hundred KB", trimmed to the time budget of this file)
+        "long blocks in both orders": {j[6] for j in plan.jobs if j[3] >= 65280} == {0, 1},
+        "reads without an array between reads with one": b"\xff" * 90 in want,
+    }
+    assert all(reached.values()), [k for k, v in reached.items() if not v]
+
+
+@pytest.mark.parametrize("variant", ["multi_ref", "lossy record", "shared QS block"])
+def test_gates_around_the_block(variant, emul, tmp_path, monkeypatch):
+    """multi-reference slices of mapped reads go to the device; a slice with a lossy-quality record, and a quality block that a second series reads, stay on the host"""
+    if variant == "shared QS block":
+        slices = [s for s in qualgen.shapes() if s.name.startswith(("size 2048", "binned 4"))]
+        for s in slices: s.gate = variant
+        monkeypatch.setattr(CE, "QS_SHARED_BLOCK", True)
+        made = qualgen.write(slices, str(tmp_path), "shared")
+    else:
+        slices = qualgen.mapped_slices()
+        if variant == "lossy record":
+            for s in slices: s.gate = variant
+        made = qualgen.write(slices, str(tmp_path), "mapped", multi_ref=True, qual_features=variant == "lossy record")
+    f = CD.read_cram(made["cram"])
+    if variant == "multi_ref": assert all(sh.ref_id == -2 for _, ss, _ in f.containers for sh in ss)
+    if variant == "lossy record": assert sum(1 for r in f.records if not r.cf & CD.CF_QUAL_ARRAY and any(c in "Qq" for c, _, _ in r.features)) >= len(slices)
+    plan, facts, _ = check_file(emul, made, str(tmp_path), monkeypatch)
+    assert len(plan.jobs) == (len(slices) if variant == "multi_ref" else 0)
+
+
+# quality blocks of the reference's own CRAM files (htslib's writer) that the device decodes - tests/test_gpu_cram_quals.py asserts the same numbers on the GPU
+FIXTURE_JOBS = {"SampleIdentity_in_rna.cram": 3, "cramTest.cram": 7}
+
+
+@pytest.mark.parametrize("name", list(FIXTURE_JOBS))
+def test_htslib_written_fixtures(name, emul, tmp_path, monkeypatch):
+    """every quality block of the fixture that is large enough is a job; the jobs of up to 100 000 bytes run under the emulator
+    (the larger ones would take this file over its time budget: the GPU test decodes them all) against the sequential reference, rans_decode on the block, and the
+    bytes the host-only path wrote into the records"""
+    src = os.path.join(GI, name); cram = open(src, "rb").read()
+    want, blank, plan = product(src, str(tmp_path), monkeypatch)
+    assert len(plan.jobs) == FIXTURE_JOBS[name]
+    sub = plan.copy(); sub.jobs = [j for j in sub.jobs if j[3] <= 100000]; sub.patches = [p for p in sub.patches if any(j[1] <= p[1] < j[1] + j[3] for j in sub.jobs)]
+    assert sub.jobs and sub.patches
+    qs, jst, got, pst = run(emul, sub, cram, blank)
+    for k, (job, (rst, rdata, _)) in enumerate(zip(sub.jobs, R.decode_jobs(sub, cram))):
+        assert jst[k] == (0, 0) and rst == 0 and qs[job[1]:job[1] + job[3]] == rdata == CD.rans_decode(rans_block_of(cram, job)), k
+    assert pst == (0, 0)
+    for dst, src_, ln, _ in sub.patches: assert got[dst:dst + ln] == want[dst:dst + ln] and not any(blank[dst:dst + ln])
+    untouched = bytearray(got)
+    for dst, src_, ln, _ in sub.patches: untouched[dst:dst + ln] = blank[dst:dst + ln]
+    assert bytes(untouched) == blank
+
+
+# ---- damaged plans ----
+def _small_jobs(plan, limit=2700):
+    return [k for k, j in enumerate(plan.jobs) if j[3] <= limit]
+
+
+def test_damaged_plans(emul, tmp_path, monkeypatch):
+    """bit flips in the byte stream and in the four states, states below the renormalisation bound, shortened streams (15, 16, inside), a zeroed table row, nsym 0 and
+    65, a context 0 that is no symbol: the run ends, nothing outside the job's ranges is touched, and either the status bit says why or the output is the sequential
+    reference's reading of the same plan"""
+    slices = qualgen.shapes(big=False); made = qualgen.write(slices, str(tmp_path), "shapes")
+    cram0 = open(made["cram"], "rb").read(); _, blank, plan0 = product(made["cram"], str(tmp_path), monkeypatch)
+    rng = random.Random(41); small = _small_jobs(plan0); assert len(small) >= 30
+    cram = bytearray(cram0); plan = plan0.copy(); plan.jobs = []; plan.patches = []; plan.out_bytes = 0; modes = []
+    MODES = ["stream bits", "state bits", "small state", "in_len 15", "in_len 16", "in_len inside", "zero row", "nsym 0", "nsym 65", "context 0"]
+    for n in range(300):
+        j = list(plan0.jobs[small[(n // len(MODES) * 7 + n) % len(small)]]); mode = MODES[n % len(MODES)]
+        at = len(cram); cram += cram0[j[0]:j[0] + j[2]]; j[0] = at; j[1] = plan.out_bytes; plan.out_bytes += j[3]
+        if mode == "stream bits":
+            for _ in range(rng.randrange(1, 4)): cram[at + rng.randrange(16 if j[2] > 16 else 0, j[2])] ^= 1 << rng.randrange(8)
+        elif mode == "state bits": cram[at + rng.randrange(16)] ^= 1 << rng.randrange(8)
+        elif mode == "small state":
+            s = rng.randrange(4); v = rng.choice([0, 0, rng.randrange(4096), rng.randrange(1 << 23)]); cram[at + 4 * s:at + 4 * s + 4] = struct.pack("<I", v)
+        elif mode == "in_len 15": j[2] = 15
+        elif mode == "in_len 16": j[2] = 16
+        elif mode == "in_len inside": j[2] = rng.randrange(17, max(18, j[2]))
+        elif mode == "zero row":
+            row = j[7] + 1; r = rng.randrange(j[7]) if j[6] else 0; t0 = len(plan.tabs); rows = j[7] if j[6] else 1
+            plan.tabs += plan0.tabs[j[4]:j[4] + rows * row]; j[4] = t0
+            for k in range(row): plan.tabs[t0 + r * row + k] = 0
+        elif mode == "nsym 0": j[7] = 0
+        elif mode == "nsym 65": j[7] = 65
+        elif mode == "context 0":
+            s0 = len(plan.syms); plan.syms += plan0.syms[j[5]:j[5] + 320]; j[5] = s0; plan.syms[s0 + 64] = rng.choice([j[7], 64, 255])
+        plan.jobs.append(j); modes.append(mode)
+    qs, jst, _, _ = run(emul, plan, bytes(cram), b"")
+    ref = R.decode_jobs(plan, bytes(cram)); flagged = {}; equal = {}
+    for k, (j, mode, (rst, rdata, _)) in enumerate(zip(plan.jobs, modes, ref)):
+        st, findings = jst[k]
+        assert findings == 0, "job %d (%s): emulator findings %d" % (k, mode, findings)
+        gate = j[2] < 16 or not 1 <= j[7] <= 64
+        if st: assert st == (R.ST_JOB if gate else R.ST_STREAM), (k, mode, st)
+        else: assert rst == 0 and qs[j[1]:j[1] + j[3]] == rdata, "job %d (%s): status 0, but the output is not the sequential reference's (%s)" % (k, mode, "which refuses the plan" if rst else "differs")
+        if mode == "small state": assert st == R.ST_STREAM, "job %d: a start state below 2^23 is refused (the rounds give a state at most three bytes)" % k
+        if rst: assert st == rst, "job %d (%s): the sequential reference refuses it (%d), the kernel says %d" % (k, mode, rst, st)
+        (flagged if st else equal)[mode] = (flagged if st else equal).get(mode, 0) + 1
+    assert all(flagged.get(m, 0) == 30 for m in ("in_len 15", "nsym 0", "nsym 65")) and all(flagged.get(m, 0) >= 5 for m in ("zero row", "context 0", "in_len inside"))   # (a row no state ever enters, context 0 in an order-0 job: no damage)
+    assert flagged.get("stream bits", 0) + equal.get("stream bits", 0) == 30 and equal.get("stream bits", 0) >= 1 and flagged.get("small state", 0) >= 1
+
+
+def test_damaged_patches(emul, tmp_path, monkeypatch):
+    """a record whose qualities lie behind the decoded bytes (bit 4) or behind the image (bit 8): nothing of it is copied, every other record is"""
+    slices = [s for s in qualgen.shapes(big=False) if s.name.startswith(("size 2048", "size 2049", "binned"))]; made = qualgen.write(slices, str(tmp_path), "few")
+    cram = open(made["cram"], "rb").read(); want, blank, plan0 = product(made["cram"], str(tmp_path), monkeypatch)
+    rng = random.Random(43); qs = b"".join(s.quals() for s in slices); assert len(qs) == plan0.out_bytes
+    members = (len(blank) + 65279) // 65280; image_bytes = (members - 1) * 65311 + 23 + (len(blank) - (members - 1) * 65280) + 8
+    plan0.jobs = []                                                     # (the second kernel alone, on the qualities themselves)
+    assert run(emul, plan0, cram, blank, qs)[2] == want
+    for n in range(40):
+        plan = plan0.copy(); k = rng.randrange(len(plan.patches)); p = plan.patches[k]
+        if n % 2 == 0: p[1] = plan.out_bytes - p[2] + rng.choice([1, 1, 2, 1000, 1 << 40]); bit = R.ST_SRC
+        else: p[0] = len(blank) + 8 + rng.choice([0, 0, 1, 31, 100000, 1 << 40]); bit = R.ST_DST   # (behind the last member's trailer: the end of the image the kernel is given)
+        _, _, got, pst = run(emul, plan, cram, blank, qs)
+        rst, rstream = R.patch_stream(plan, qs, blank, image_bytes)
+        assert pst == (bit, 0) and rst == bit and got == rstream, (n, pst, rst)
+    plan = plan0.copy(); plan.patches[0][1] = plan.out_bytes - plan.patches[0][2]              # the last decoded byte is the patch's last: not an error
+    assert run(emul, plan, cram, blank, qs)[3] == (0, 0)
