@@ -87,8 +87,9 @@ int ngsqc_cram_to_bam(const char* cram_path, const char* bam_path, const ngsqc_n
 		for (int64_t i = 0; i < n_regions; ++i) sel.regions.push_back(ngsqc::CramSelect::Region{regions[i].chr ? regions[i].chr : "", regions[i].start, regions[i].end});
 		// NGSQC_CRAM_PLAN_DUMP=<file> (tests): the records with the quality arrays left blank, as the device path uploads them, and the plan of the quality blocks in <file>
 		// (counts, then the arrays of CramQualPlan) - tests/test_cpu_cram.py replays the device kernels of cram_dev.hip on it
-		const char* dump = getenv("NGSQC_CRAM_PLAN_DUMP"); ngsqc::CramQualPlan plan;
-		const int rc = ngsqc::cram_to_bam_image(d.data(), d.size(), cram_path, image, err, &sel, dump ? &plan : nullptr);
+		// (no device and no handle here: the same table, read the same way)
+		const ngsqc::OpenSwitches sw; const char* dump = sw.cram_plan_dump.empty() ? nullptr : sw.cram_plan_dump.c_str(); ngsqc::CramQualPlan plan;
+		const int rc = ngsqc::cram_to_bam_image(d.data(), d.size(), cram_path, image, err, sw, &sel, dump ? &plan : nullptr);
 		if (rc != NGSQC_OK) { g_open_error = err; return rc; }
 		if (dump)
 		{
@@ -203,8 +204,8 @@ int ngsqc_copy_record_offsets(ngsqc_handle* h, int64_t* out, int64_t cap)
 static ngsqc_timings timings_of(const ngsqc_handle* h)
 {
 	ngsqc_timings t = h->tm;
-	const char* e1 = getenv("NGSQC_CRAM_IGNORE_MD5"); const char* e2 = getenv("NGSQC_CRAM_NO_REFERENCE");
-	t.switches = (h->verify_crc ? NGSQC_SW_VERIFY_CRC : 0) | (e1 && atoi(e1) != 0 ? NGSQC_SW_CRAM_IGNORE_MD5 : 0) | (e2 && atoi(e2) != 0 ? NGSQC_SW_CRAM_NO_REFERENCE : 0);
+	// (what the handle was opened with, not the environment of this moment)
+	t.switches = (h->verify_crc ? NGSQC_SW_VERIFY_CRC : 0) | (h->osw.cram_ignore_md5 ? NGSQC_SW_CRAM_IGNORE_MD5 : 0) | (h->osw.cram_no_reference ? NGSQC_SW_CRAM_NO_REFERENCE : 0);
 	return t;
 }
 int ngsqc_get_timings(const ngsqc_handle* h, ngsqc_timings* t) { if (!h || !t) return NGSQC_E_ARG; *t = timings_of(h); return NGSQC_OK; }

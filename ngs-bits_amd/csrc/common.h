@@ -11,6 +11,7 @@
 #include "../../include/ngsqc.h"
 #include "k1_types.h"
 #include "cram_plan.h"
+#include "switches.h"
 
 namespace ngsqc {
 
@@ -22,7 +23,7 @@ constexpr int NAME_SHIFT = 12;       // a record of a tile scanned by the chain 
 // two-phase K1 (k1_kernels.h / inflate.hip): lane-per-member Huffman -> token groups in pages of a pool, then wave-per-member LZ77 resolve
 void launch_huff_tokens(const uint8_t* d_comp, const BlockDesc* d_blocks, int64_t n_blocks, BlockStatus* d_status,
                         uint32_t* d_pool, uint32_t pool_pages, uint32_t* d_pool_ctr /* zeroed */, uint32_t* d_tok_first, uint32_t* d_tok_count,
-                        unsigned long long* d_work /* zeroed */, const uint32_t* d_order /* queue order inside the launch, or null */, int max_wgs, hipStream_t s);
+                        unsigned long long* d_work /* zeroed */, const uint32_t* d_order /* queue order inside the launch, or null */, int max_wgs, int park /* OpenSwitches::p1_park */, hipStream_t s);
 void launch_lz77_resolve(const BlockDesc* d_blocks, int64_t n_blocks, uint8_t* d_out, BlockStatus* d_status,
                          const uint32_t* d_pool, const uint32_t* d_tok_first, const uint32_t* d_tok_count, const uint8_t* d_comp, hipStream_t s);
 
@@ -59,7 +60,6 @@ inline std::string chr_norm(std::string c)
 // CRAM 3.0 input (cram.hip; host only): the file as a BAM stream / as a BGZF image with stored blocks that the BAM path takes like any other BAM
 bool is_cram(const uint8_t* d, size_t n);
 void cram_set_reference(const char* fasta);
-std::string cram_reference();
 int cram_set_skip_thread(int flags);   // the calling thread's own choice (-1: none); returns the previous one
 void cram_set_skip(int flags);   // bit 0: read names, bit 1: optional fields are not needed (not decoded where their blocks are theirs alone)
 int cram_skip();
@@ -75,14 +75,12 @@ struct ByteImage
 	size_t size() const { return n; }
 };
 // the CRAM as a BAM IMAGE: header + records in BGZF members of 65 280 bytes with stored blocks (+ the EOF member), which the BAM path takes like any other BAM
-int cram_to_bam_image(const uint8_t* d, size_t n, const std::string& path, ByteImage& image, std::string& err, const CramSelect* sel = nullptr, CramQualPlan* defer = nullptr);   // NGSQC_OK or an NGSQC_E_* code with err
+int cram_to_bam_image(const uint8_t* d, size_t n, const std::string& path, ByteImage& image, std::string& err, const OpenSwitches& sw, const CramSelect* sel = nullptr, CramQualPlan* defer = nullptr);   // NGSQC_OK or an NGSQC_E_* code with err
 // decodes the plan's blocks on the device and writes the qualities into the BAM image (stored BGZF members of 65 280 bytes, as bgzf_store lays them out) at d_image; returns the kernel time in ms
 double cram_device_quals(const uint8_t* cram_image, const CramQualPlan& plan, uint8_t* d_image, size_t image_bytes, hipStream_t s);
 
-void k1_read_switches();   // NGSQC_P1_PARK (read when a handle is opened)
-
 // CRC32 of every inflated member against its BGZF trailer (crc.hip); a mismatch sets status.error = K1_ERR_CRC
-void launch_crc32(const BlockDesc* d_blocks, int64_t n_blocks, const uint8_t* d_out, const uint32_t* d_expected, BlockStatus* d_status, hipStream_t s);
+void launch_crc32(const BlockDesc* d_blocks, int64_t n_blocks, const uint8_t* d_out, const uint32_t* d_expected, BlockStatus* d_status, int chains /* per lane: 1, 2 or 4 (CallSwitches::crc_chains) */, hipStream_t s);
 
 // ---- K2 ----
 // (n_entries = members << ksh, + 1 for the carried prefix; every array is indexed by entry)
@@ -146,7 +144,7 @@ struct ScanParams
 
 void launch_scan(const ScanParams& p, hipStream_t s);
 // K2's chain walk (what launch_index_count does) with the scan of every record the walk passes: one read of a record's first line instead of two
-void launch_walk_scan(const ScanParams& p, const BlockDesc* d_blocks, int64_t n_entries, int64_t prefix, int ksh, int64_t nm, int32_t* d_start, uint32_t* d_cnt, int64_t* d_next_abs, uint32_t* d_bad, uint16_t* d_rel, hipStream_t s);
+void launch_walk_scan(const ScanParams& p, const BlockDesc* d_blocks, int64_t n_entries, int64_t prefix, int ksh, int64_t nm, int32_t* d_start, uint32_t* d_cnt, int64_t* d_next_abs, uint32_t* d_bad, uint16_t* d_rel, int waves /* CallSwitches::walk_waves */, hipStream_t s);
 void launch_index_guess(const uint8_t* d_infl, int64_t total, const BlockDesc* d_blocks, int64_t n_entries, int64_t prefix, int ksh, int64_t nm, int64_t from, int32_t* d_start, int32_t n_ref, hipStream_t s);
 void launch_scan_long(const ScanParams& p, int64_t n_long, hipStream_t s);
 void launch_baseq_list(const ScanParams& p, int64_t n, hipStream_t s, int64_t* d_sorted, void* d_tmp, size_t tmp_bytes);   // the min_baseq mask of the n records in p.bq_list (sorted by offset into d_sorted first)

@@ -1155,12 +1155,7 @@ template <class F> void parallel_for(size_t n, int threads, F fn)
 	for (auto& t : pool) t.join();
 	if (err) std::rethrow_exception(err);
 }
-int host_threads()
-{
-	int nt = (int)std::min<size_t>(std::max(1u, std::thread::hardware_concurrency()), 32);
-	if (const char* et = getenv("NGSQC_CRAM_THREADS")) nt = std::max(1, atoi(et));
-	return nt;
-}
+int host_threads(const OpenSwitches& sw) { return sw.cram_threads ? sw.cram_threads : (int)std::min<size_t>(std::max(1u, std::thread::hardware_concurrency()), 32); }
 
 struct SliceJob
 {
@@ -1172,19 +1167,18 @@ std::mutex g_ref_mu; std::string g_reference;
 } // namespace
 
 void cram_set_reference(const char* fasta) { std::lock_guard<std::mutex> g(g_ref_mu); g_reference = fasta ? fasta : ""; }
-std::string cram_reference()
+static std::string cram_reference(const OpenSwitches& sw)
 {
 	{ std::lock_guard<std::mutex> g(g_ref_mu); if (!g_reference.empty()) return g_reference; }
-	const char* e = getenv("NGSQC_REFERENCE");
-	return e ? e : "";
+	return sw.reference;
 }
 bool is_cram(const uint8_t* d, size_t n) { return n >= 4 && memcmp(d, "CRAM", 4) == 0; }
 
 namespace {
 // the whole CRAM as an uncompressed BAM stream ("BAM\1", header, records in file order). Throws FormatError / IoError / std::domain_error.
-void bgzf_store_pieces(const std::vector<std::pair<const uint8_t*, size_t>>& pieces, ByteImage& image);
+void bgzf_store_pieces(const std::vector<std::pair<const uint8_t*, size_t>>& pieces, ByteImage& image, int threads);
 
-void cram_to_bam_stream_impl(const uint8_t* d, size_t n, const std::string& path, ByteImage& image, const CramSelect* sel, CramQualPlan* defer)
+void cram_to_bam_stream_impl(const uint8_t* d, size_t n, const std::string& path, ByteImage& image, const OpenSwitches& sw, const CramSelect* sel, CramQualPlan* defer)
 {
 	std::vector<uint8_t> stream;   // (the BAM header only: the records stay in the slices' buffers until they are framed)
 	try
@@ -1275,14 +1269,13 @@ void cram_to_bam_stream_impl(const uint8_t* d, size_t n, const std::string& path
 		(void)eof;   // (htslib warns about a missing EOF container and goes on)
 		// ---- the genome ----
 		DecodeEnv env; env.ref_names = &ref_names; env.rg_ids = &rg_ids; env.path = path;
-		const char* e1 = getenv("NGSQC_CRAM_NO_REFERENCE"); env.no_reference = e1 && atoi(e1) != 0;
-		const char* e2 = getenv("NGSQC_CRAM_IGNORE_MD5"); env.ignore_md5 = e2 && atoi(e2) != 0;
+		env.no_reference = sw.cram_no_reference; env.ignore_md5 = sw.cram_ignore_md5;
 		RefGenome genome;
 		bool need_genome = false;   // a slice of mapped reads whose bases are neither all in the file (RR = false) nor in an embedded reference block
 		for (const SliceJob& j : jobs) need_genome = need_genome || (j.ch->RR && j.sh.embedded_ref < 0 && j.sh.ref_id != -1);
 		if (any_rr && need_genome && !env.no_reference)
 		{
-			const std::string fasta = cram_reference(); std::string err;
+			const std::string fasta = cram_reference(sw); std::string err;
 			if (fasta.empty() || !genome.open(fasta, err)) throw IoError("Error while setting reference genome '" + fasta + "'for cram file " + path);   // BamReader.cpp:486-489
 			// checkChromosomeLengths (BamReader.cpp:491): the genome must hold the file's sequences at their lengths
 			for (size_t i = 0; i < ref_names.size(); ++i)
@@ -1296,7 +1289,7 @@ void cram_to_bam_stream_impl(const uint8_t* d, size_t n, const std::string& path
 		{ int64_t n_records = 0; for (const SliceJob& j : jobs) n_records += j.sh.n_records; if (n_records > 100000000ll) defer = nullptr; }
 		const double t_parse = since();
 		// ---- slices in parallel ----
-		const int nthreads = (int)std::min<size_t>((size_t)host_threads(), std::max<size_t>(jobs.size(), 1));
+		const int nthreads = (int)std::min<size_t>((size_t)host_threads(sw), std::max<size_t>(jobs.size(), 1));
 		std::atomic<size_t> next(0); std::mutex err_mu; std::exception_ptr first_err;
 		std::atomic<long long> us_blocks(0), us_records(0);   // (summed over the workers: NGSQC_TIMING)
 		auto now_us = [] { return (long long)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
@@ -1350,7 +1343,7 @@ void cram_to_bam_stream_impl(const uint8_t* d, size_t n, const std::string& path
 		std::vector<std::pair<const uint8_t*, size_t>> pieces; pieces.emplace_back(stream.data(), stream.size());
 		for (size_t ji = 0; ji < jobs.size(); ++ji) { base_of[ji] = at; at += jobs[ji].out.size(); pieces.emplace_back(jobs[ji].out.data(), jobs[ji].out.size()); }
 		const size_t stream_bytes = (size_t)at;
-		bgzf_store_pieces(pieces, image);   // (header + the slices' records, cut into stored BGZF members - in parallel, straight out of the slices' buffers)
+		bgzf_store_pieces(pieces, image, host_threads(sw));   // (header + the slices' records, cut into stored BGZF members - in parallel, straight out of the slices' buffers)
 		for (SliceJob& j : jobs) std::vector<uint8_t>().swap(j.out);
 		for (size_t ji = 0; ji < jobs.size(); ++ji)
 		{
@@ -1364,7 +1357,7 @@ void cram_to_bam_stream_impl(const uint8_t* d, size_t n, const std::string& path
 				defer->out_bytes += q.n_out; ++n_q;
 			}
 		}
-		if (getenv("NGSQC_TIMING"))
+		if (sw.timing)
 			fprintf(stderr, "[ngsqc] cram: %zu slices on %d host threads: structure %.1f ms, blocks + records %.1f ms, BAM stream of %zu bytes %.1f ms; quality blocks left to the device: %zu (%llu bytes); summed over the threads: CRC + block codecs %.1f ms, records %.1f ms\n",
 			        jobs.size(), nthreads, t_parse, t_decode - t_parse, stream_bytes, since() - t_decode, n_q, defer ? (unsigned long long)defer->out_bytes : 0ull, (double)us_blocks.load() / 1e3, (double)us_records.load() / 1e3);
 	}
@@ -1373,10 +1366,10 @@ void cram_to_bam_stream_impl(const uint8_t* d, size_t n, const std::string& path
 } // namespace
 
 // NGSQC_OK or NGSQC_E_FORMAT / NGSQC_E_IO / NGSQC_E_UNSUPPORTED / NGSQC_E_DEVICE with the message in err
-int cram_to_bam_image(const uint8_t* d, size_t n, const std::string& path, ByteImage& image, std::string& err, const CramSelect* sel, CramQualPlan* defer)
+int cram_to_bam_image(const uint8_t* d, size_t n, const std::string& path, ByteImage& image, std::string& err, const OpenSwitches& sw, const CramSelect* sel, CramQualPlan* defer)
 {
 	if (defer) *defer = CramQualPlan();
-	try { cram_to_bam_stream_impl(d, n, path, image, sel, defer); return NGSQC_OK; }
+	try { cram_to_bam_stream_impl(d, n, path, image, sw, sel, defer); return NGSQC_OK; }
 	catch (FormatError& e) { err = e.what(); return NGSQC_E_FORMAT; }
 	catch (IoError& e) { err = e.what(); return NGSQC_E_IO; }
 	catch (std::domain_error& e) { err = e.what(); return NGSQC_E_UNSUPPORTED; }
@@ -1387,13 +1380,13 @@ int cram_to_bam_image(const uint8_t* d, size_t n, const std::string& path, ByteI
 namespace {
 // the concatenation of the pieces in BGZF members with STORED deflate blocks (RFC 1951 3.2.4) and the EOF member: what K1's stored-block path copies on the device.
 // Member m holds stream bytes [m * 65280, ...): 18 bytes of header, 5 of the stored block, the bytes, CRC-32 and size - every member at a known place, filled in parallel.
-void bgzf_store_pieces(const std::vector<std::pair<const uint8_t*, size_t>>& pieces, ByteImage& image)
+void bgzf_store_pieces(const std::vector<std::pair<const uint8_t*, size_t>>& pieces, ByteImage& image, int threads)
 {
 	std::vector<uint64_t> start(pieces.size() + 1, 0);
 	for (size_t i = 0; i < pieces.size(); ++i) start[i + 1] = start[i] + pieces[i].second;
 	const uint64_t total = start.back(); const size_t piece = 0xff00, nm = (size_t)((total + piece - 1) / piece);
 	image.make((size_t)total + nm * 31 + 28);
-	parallel_for(nm, host_threads(), [&](size_t m) {
+	parallel_for(nm, threads, [&](size_t m) {
 		const uint64_t s0 = (uint64_t)m * piece; const size_t n = (size_t)std::min<uint64_t>(piece, total - s0);
 		uint8_t* o = image.data() + m * (piece + 31);
 		const uint32_t bsize = (uint32_t)(n + 5 + 25);

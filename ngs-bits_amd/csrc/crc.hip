@@ -265,12 +265,11 @@ const uint32_t* crc_device_tables()
 	return d_tab[dev];
 }
 
-void launch_crc32(const BlockDesc* d_blocks, int64_t n_blocks, const uint8_t* d_out, const uint32_t* d_expected, BlockStatus* d_status, hipStream_t s)
+void launch_crc32(const BlockDesc* d_blocks, int64_t n_blocks, const uint8_t* d_out, const uint32_t* d_expected, BlockStatus* d_status, int chains, hipStream_t s)
 {
 	if (n_blocks <= 0) return;
 	const uint32_t* tabs = crc_device_tables();
 	const int64_t wgs = (n_blocks + 3) / 4;
-	const char* e = getenv("NGSQC_CRC_CHAINS"); const int chains = e && (atoi(e) == 1 || atoi(e) == 2) ? atoi(e) : 4;   // chains per lane (1: the round-2 kernel); read per launch so that one process can compare them
 	const dim3 grid((unsigned)(wgs < 32768 ? wgs : 32768)), wg(256);
 	if (chains == 4) hipLaunchKernelGGL(crc32_chains_kernel<4>, grid, wg, 0, s, d_blocks, n_blocks, d_out, d_expected, d_status, tabs);
 	else if (chains == 2) hipLaunchKernelGGL(crc32_chains_kernel<2>, grid, wg, 0, s, d_blocks, n_blocks, d_out, d_expected, d_status, tabs);

@@ -265,11 +265,11 @@ void bam_to_fastq(ngsqc_handle* h, const ngsqc_fastq_params* fp, const char* out
 	if (fp->compression_level < 0 || fp->compression_level > 9) throw ArgError("compression level " + std::to_string(fp->compression_level) + " is not in 0..9");
 	if (fp->reg_tid >= (int32_t)h->ref_names.size()) throw ArgError("region reference id out of range");
 	const bool paired = out2 && *out2;
-	FqParams p{fp->remove_duplicates ? 1 : 0, fp->fix ? 1 : 0, std::max(0, fp->extend), paired ? 1 : 0, fp->reg_tid, fp->reg_start, fp->reg_end, name_hash_mask() >> 1};   // (a 62-bit hash: (hash << 1 | read 1) never equals KEY_NONE)
-	const bool timing = getenv("NGSQC_TIMING") != nullptr;
+	FqParams p{fp->remove_duplicates ? 1 : 0, fp->fix ? 1 : 0, std::max(0, fp->extend), paired ? 1 : 0, fp->reg_tid, fp->reg_start, fp->reg_end, name_hash_mask(h->sw.name_hash_bits) >> 1};   // (a 62-bit hash: (hash << 1 | read 1) never equals KEY_NONE)
+	const bool timing = h->sw.timing;
 	hipStream_t s = h->stream;
 	const char* T = "BamToFastq";
-	const int64_t W = write_window_bytes();
+	const int64_t W = write_window_bytes(h->sw.write_window_pieces);
 	BgzfStream o1(T, W, fp->compression_level), o2(T, W, fp->compression_level);
 	o1.sink.open(out1, std::string("Could not open file '") + out1 + "' for writing!");
 	if (paired) o2.sink.open(out2, std::string("Could not open file '") + out2 + "' for writing!");

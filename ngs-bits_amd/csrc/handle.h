@@ -139,7 +139,7 @@ inline uint32_t rd32(const uint8_t* p) { return (uint32_t)p[0] | ((uint32_t)p[1]
 constexpr int K1_CHUNK_WAVES_PER_CU = 5;   // a K1 chunk = this many decoder waves per CU (x 64 members). Round 6: HALF of what a CU holds - two decoder launches run side by side (the two phase-1 streams), and a
                                           // chunk of 6 with room for 10 left the second launch with four waves per CU until the first was done: the full-size step 506 -> 446 ms with 5 (profiles/r06_schedule_probe.txt)
 constexpr int P1_WAVES_PER_CU = 10;       // decoder waves a CU holds (15.4 KB LDS each since the token lines are staged there, round 6; 193 VGPRs = two per SIMD)
-constexpr int K1_SLOTS_DEFAULT = 8;  // token ring: chunk c uses slot c % slots (phase 1 of the next chunks runs while phase 2 of c reads; round 6: a fourth slot is worth 1.5 % of the full-size step with chunks of 5 waves per CU - 458 -> 451 ms, a fifth 0.4 %; eight - the most the ring holds - with eight chunks per tile); NGSQC_TOKEN_SLOTS
+// NGSQC_TOKEN_SLOTS (switches.h; default 8), the token ring: chunk c uses slot c % slots (phase 1 of the next chunks runs while phase 2 of c reads; round 6: a fourth slot is worth 1.5 % of the full-size step with chunks of 5 waves per CU - 458 -> 451 ms, a fifth 0.4 %; eight - the most the ring holds - with eight chunks per tile)
 constexpr int N_DEPTH_SETS = 2;      // [0] the mapping scan's target region, [1] the extra depth scan of a job (-somatic_custom_bed)
 
 // target regions + per-base depth of one scan
@@ -158,6 +158,8 @@ using namespace ngsqc::lib;
 
 struct ngsqc_handle
 {
+	const OpenSwitches osw;   // the environment when ngsqc_open* made the handle (switches.h): all that the open path, the layout thread and the copier threads know of it
+	CallSwitches sw;          // ... at the top of the running entry point (guarded)
 	std::string err, path;
 	bool from_cram = false;                        // the image is the BAM stream the host made of a CRAM 3.0 file (cram.hip)
 	bool selection = false;                        // opened for a range, regions or the first records (a CRAM keeps only the slices they need, and is then laid out like a whole file)
@@ -183,7 +185,7 @@ struct ngsqc_handle
 	int p1_wgs = 0;                                    // decoder workgroups a launch may keep resident
 	DevBuf<uint32_t> d_sync_pool; DevBuf<BlockDesc> d_sync_desc; DevBuf<uint32_t> d_sync_u32; DevBuf<BlockStatus> d_sync_st; DevBuf<unsigned long long> d_sync_work;   // scratch of inflate_sync (kept: a hipFree waits for every queued kernel)
 	static constexpr int MAX_TILE_BUFS = 4;
-	int k1_slots = K1_SLOTS_DEFAULT;
+	int k1_slots = osw.token_slots;
 	DevBuf<uint8_t> buf[MAX_TILE_BUFS]; int nbuf = 2;
 	int64_t max_tile_members = 0;   // tile buffers (tile t lives in buf[t % nbuf]): [pfx carried bytes right-aligned][members][64]
 	std::vector<hipEvent_t> ev_chunk;                  // 4 per chunk: p1 start/end, p2 start/end
@@ -208,7 +210,7 @@ struct ngsqc_handle
 	int64_t shard_limit = -1;              // rebased inflated offset of the first byte that is NOT owned
 	int64_t shard_u_base = 0;              // inflated offset (whole file) of the handle's first member
 	int64_t shard_first_abs = -1, shard_exit_abs = -1; int shard_last_tile = -1;
-	bool verify_crc = true;
+	bool verify_crc = osw.verify_crc;   // (false for the image made of a CRAM whose qualities the device decodes, whatever the switch says)
 	// H2D of the compressed image in the background (ngsqc_open of a path): host threads copy pieces in file order, every piece has an event that
 	// the K1 chunk stream waits for; the mapping of the file lives until the last piece is on the device
 	struct Upload
@@ -255,17 +257,18 @@ struct ngsqc_handle
 };
 
 namespace ngsqc { namespace lib {
-// NGSQC_DEBUG: where the wall time of an open goes (ms since the first stamp of the process)
-inline void dbg_stamp(const char* what)
+// NGSQC_DEBUG (on: osw.debug on the open path and its threads, sw.debug in a job): where the wall time of an open goes (ms since the first stamp of the process)
+inline void dbg_stamp(bool on, const char* what)
 {
-	static const bool on = getenv("NGSQC_DEBUG") != nullptr; static const double t0 = wall_ms();
+	static const double t0 = wall_ms();
 	if (on) fprintf(stderr, "[ngsqc] t+%.1f ms %s\n", wall_ms() - t0, what);
 }
 
-// every entry point that works on a handle: the device of the handle, exceptions -> return code + message
+// every entry point that works on a handle: the call's switches, the device of the handle, exceptions -> return code + message
 template <typename F> int guarded(ngsqc_handle* h, F f)
 {
 	if (!h) return NGSQC_E_ARG;
+	h->sw = CallSwitches();
 	try { HIPCHK(hipSetDevice(h->device)); f(); return NGSQC_OK; }
 	catch (FormatError& e) { h->err = e.what(); return NGSQC_E_FORMAT; }
 	catch (ArgError& e) { h->err = e.what(); return NGSQC_E_ARG; }
@@ -276,7 +279,7 @@ template <typename F> int guarded(ngsqc_handle* h, F f)
 
 // ---- image.hip: the BGZF member table, the BAM header, the compressed image on its way to the device, the layout of the tile stream, open ----
 void walk_bgzf(const uint8_t* file, size_t n, size_t& off, size_t off_end, int64_t max_members, uint64_t& upos, std::vector<BlockDesc>& blocks, std::vector<uint32_t>& crc, std::vector<uint64_t>* file_off = nullptr);
-void scan_bgzf(const uint8_t* file, size_t n, std::vector<BlockDesc>& blocks, std::vector<uint32_t>& crc, int64_t& total, std::vector<uint64_t>* file_off = nullptr, int threads = 0, bool* in_pieces = nullptr);
+void scan_bgzf(const uint8_t* file, size_t n, std::vector<BlockDesc>& blocks, std::vector<uint32_t>& crc, int64_t& total, std::vector<uint64_t>* file_off, int threads, bool* in_pieces = nullptr);
 std::string inflate_error(const ngsqc_handle* h, int64_t member, uint32_t code);
 void inflate_sync(ngsqc_handle* h, const std::vector<int64_t>& idx, const std::vector<BlockDesc>& desc, uint8_t* d_out, int level = 0);
 void upload_wait(ngsqc_handle* h, size_t end_byte, hipStream_t st, int slot);

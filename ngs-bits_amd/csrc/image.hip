@@ -97,7 +97,6 @@ void scan_bgzf(const uint8_t* file, size_t n, std::vector<BlockDesc>& blocks, st
 {
 	if (in_pieces) *in_pieces = false;
 	if (n >= 4 && memcmp(file, "CRAM", 4) == 0) throw std::domain_error("a CRAM file has no BGZF members: ngsqc_open / ngsqc_open_memory decode it (cram.hip)");
-	if (threads <= 0) { threads = 8; if (const char* e = getenv("NGSQC_WALK_THREADS")) threads = std::min(64, std::max(1, atoi(e))); }   // (round 4: on by default - the first job races the copy, tests/test_gpu_tools.py)
 	if (threads > 1 && n >= ((size_t)threads << 20) && scan_bgzf_threads(file, n, threads, blocks, crc, total, file_off)) { if (in_pieces) *in_pieces = true; return; }
 	blocks.clear(); crc.clear(); if (file_off) file_off->clear();
 	size_t off = 0; uint64_t upos = 0;
@@ -118,16 +117,10 @@ void init_device(ngsqc_handle* h, int device)
 	HIPCHK(hipStreamCreateWithPriority(&h->stream, hipStreamNonBlocking, prio_hi));
 	HIPCHK(hipStreamCreateWithFlags(&h->s_p1[0], hipStreamNonBlocking));
 	HIPCHK(hipStreamCreateWithFlags(&h->s_p1[1], hipStreamNonBlocking));
-	{
-		const bool p2_hi = getenv("NGSQC_P2_PRIO") && atoi(getenv("NGSQC_P2_PRIO")) != 0;   // (dev: the short-lived phase-2 / CRC waves ahead of the decoder's long-lived ones when a CU's LDS frees up)
-		HIPCHK(hipStreamCreateWithPriority(&h->s_p2, hipStreamNonBlocking, p2_hi ? prio_hi : 0));
-		HIPCHK(hipStreamCreateWithPriority(&h->s_crc, hipStreamNonBlocking, p2_hi ? prio_hi : 0));
-	}
+	HIPCHK(hipStreamCreateWithPriority(&h->s_p2, hipStreamNonBlocking, 0));
+	HIPCHK(hipStreamCreateWithPriority(&h->s_crc, hipStreamNonBlocking, 0));
 	int cu = 0; if (hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cu > 0) h->n_cu = cu;
-	const int pw = getenv("NGSQC_P1_WAVES") ? std::max(1, atoi(getenv("NGSQC_P1_WAVES"))) : P1_WAVES_PER_CU;   // (dev: decoder waves per CU a launch keeps resident)
-	h->p1_wgs = h->n_cu * pw;
-	k1_read_switches();
-	if (const char* e = getenv("NGSQC_VERIFY_CRC")) h->verify_crc = atoi(e) != 0;
+	h->p1_wgs = h->n_cu * P1_WAVES_PER_CU;
 }
 
 std::string inflate_error(const ngsqc_handle* h, int64_t member, uint32_t code)
@@ -180,9 +173,9 @@ void inflate_sync(ngsqc_handle* h, const std::vector<int64_t>& idx, const std::v
 		HIPCHK(hipMemcpyAsync(h->d_sync_desc.p, dd.data(), (size_t)n * sizeof(BlockDesc), hipMemcpyHostToDevice, h->stream));
 		HIPCHK(hipMemcpyAsync(d_crc, crc.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
 		HIPCHK(hipMemsetAsync(h->d_sync_work.p, 0, 2 * sizeof(unsigned long long), h->stream));   // [queue head | pool counter]
-		launch_huff_tokens(d_comp, h->d_sync_desc.p, n, h->d_sync_st.p, h->d_sync_pool.p, (uint32_t)pages, (uint32_t*)(h->d_sync_work.p + 1), d_first, d_cnt, h->d_sync_work.p, nullptr, h->p1_wgs, h->stream);
+		launch_huff_tokens(d_comp, h->d_sync_desc.p, n, h->d_sync_st.p, h->d_sync_pool.p, (uint32_t)pages, (uint32_t*)(h->d_sync_work.p + 1), d_first, d_cnt, h->d_sync_work.p, nullptr, h->p1_wgs, h->osw.p1_park, h->stream);
 		launch_lz77_resolve(h->d_sync_desc.p, n, d_out, h->d_sync_st.p, h->d_sync_pool.p, d_first, d_cnt, d_comp, h->stream);
-		if (h->verify_crc) launch_crc32(h->d_sync_desc.p, n, d_out, d_crc, h->d_sync_st.p, h->stream);
+		if (h->verify_crc) launch_crc32(h->d_sync_desc.p, n, d_out, d_crc, h->d_sync_st.p, h->sw.crc_chains, h->stream);
 		std::vector<BlockStatus> st((size_t)n);
 		HIPCHK(hipMemcpyAsync(st.data(), h->d_sync_st.p, (size_t)n * sizeof(BlockStatus), hipMemcpyDeviceToHost, h->stream));
 		HIPCHK(hipStreamSynchronize(h->stream));
@@ -237,48 +230,16 @@ bool read_header(ngsqc_handle* h, int64_t avail)
 	}
 }
 
-// H2D of the compressed image. The source is pageable memory (an mmap of the file, a caller's buffer). One hipMemcpy of it is the default: the
-// runtime pins the pages and runs the DMA at 37-56 GB/s on a 14 GB image whose pages are warm (12 GB/s on the 60 GB image right after it was
-// generated: first pinning of cold pages). NGSQC_H2D_THREADS=T stages the image through T host threads with pinned buffer pairs instead; measured
-// slower on this host (16-CPU quota: 14 / 20 / 26 GB/s at 8 / 4 / 16 threads), kept as a switch for hosts with more cores per GPU.
+// H2D of the compressed image. The source is pageable memory (an mmap of the file, a caller's buffer): one hipMemcpy of it - the runtime pins the pages and runs the DMA
+// at 37-56 GB/s on a 14 GB image whose pages are warm (12 GB/s on the 60 GB image right after it was generated: first pinning of cold pages; DESIGN.md has the staged
+// alternative that was measured and removed).
 void upload_compressed(ngsqc_handle* h, const uint8_t* bytes, size_t beg, size_t end)
 {
 	const size_t n = end - beg;
 	h->d_comp.alloc(n + 1024);
 	HIPCHK(hipMemsetAsync(h->d_comp.p + n, 0, 1024, h->stream));
 	if (!n) return;
-	constexpr size_t PIECE = 32u << 20;
-	int T = 1; if (const char* e = getenv("NGSQC_H2D_THREADS")) T = std::max(1, atoi(e));
-	if (n < 8 * PIECE || T == 1) { HIPCHK(hipMemcpyAsync(h->d_comp.p, bytes + beg, n, hipMemcpyHostToDevice, h->stream)); HIPCHK(hipStreamSynchronize(h->stream)); return; }
-	const size_t n_pieces = (n + PIECE - 1) / PIECE;
-	std::atomic<size_t> next(0); std::vector<std::string> errs((size_t)T);
-	std::vector<std::thread> th;
-	for (int t = 0; t < T; ++t)
-		th.emplace_back([&, t] {
-			uint8_t* pin[2] = {nullptr, nullptr}; hipStream_t st = nullptr; hipEvent_t ev[2] = {nullptr, nullptr};
-			try
-			{
-				HIPCHK(hipSetDevice(h->device));
-				HIPCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-				for (int k = 0; k < 2; ++k) { HIPCHK(hipHostMalloc((void**)&pin[k], PIECE, hipHostMallocDefault)); HIPCHK(hipEventCreateWithFlags(&ev[k], hipEventDisableTiming)); }
-				for (int k = 0;; k ^= 1)
-				{
-					const size_t i = next.fetch_add(1); if (i >= n_pieces) break;
-					const size_t off = i * PIECE, sz = std::min(PIECE, n - off);
-					HIPCHK(hipEventSynchronize(ev[k]));   // the previous DMA out of this buffer is done (an unrecorded event is complete)
-					memcpy(pin[k], bytes + beg + off, sz);
-					HIPCHK(hipMemcpyAsync(h->d_comp.p + off, pin[k], sz, hipMemcpyHostToDevice, st));
-					HIPCHK(hipEventRecord(ev[k], st));
-				}
-				HIPCHK(hipStreamSynchronize(st));
-			}
-			catch (std::exception& e) { errs[(size_t)t] = e.what(); }
-			for (int k = 0; k < 2; ++k) { if (pin[k]) (void)hipHostFree(pin[k]); if (ev[k]) (void)hipEventDestroy(ev[k]); }
-			if (st) (void)hipStreamDestroy(st);
-		});
-	for (auto& t : th) t.join();
-	for (auto& e : errs) if (!e.empty()) throw std::runtime_error(e);
-	HIPCHK(hipStreamSynchronize(h->stream));
+	HIPCHK(hipMemcpyAsync(h->d_comp.p, bytes + beg, n, hipMemcpyHostToDevice, h->stream)); HIPCHK(hipStreamSynchronize(h->stream));
 }
 
 // ---- H2D in the background: pieces of the compressed image in file order, one event per piece ----
@@ -301,22 +262,22 @@ void upload_start(ngsqc_handle* h, const uint8_t* bytes, size_t beg, size_t end)
 {
 	ngsqc_handle::Upload* u = h->up;
 	const size_t n = end - beg;
-	dbg_stamp("upload: allocating the image buffer");
+	const bool dbg = h->osw.debug;
+	dbg_stamp(dbg, "upload: allocating the image buffer");
 	h->d_comp.alloc(n + 1024);
-	dbg_stamp("upload: image buffer allocated");
+	dbg_stamp(dbg, "upload: image buffer allocated");
 	HIPCHK(hipMemsetAsync(h->d_comp.p + n, 0, 1024, h->stream));
 	HIPCHK(hipStreamSynchronize(h->stream));
-	dbg_stamp("upload: first device operation done");
-	u->piece = 64u << 20; if (const char* e = getenv("NGSQC_H2D_PIECE_MB")) u->piece = (size_t)std::max(1, atoi(e)) << 20;
+	dbg_stamp(dbg, "upload: first device operation done");
+	u->piece = (size_t)h->osw.h2d_piece_mb << 20;
 	u->bytes = n; u->n_pieces = (n + u->piece - 1) / u->piece; u->next = 0; u->done = 0; u->cancel = false; u->t0 = wall_ms(); u->t_done = u->t0;
 	u->recorded.assign(u->n_pieces, 0); u->ev.assign(u->n_pieces, nullptr);
 	for (auto& e : u->ev) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-	int T = 4; if (const char* e = getenv("NGSQC_H2D_THREADS")) T = std::max(1, atoi(e));
-	T = (int)std::min<size_t>((size_t)T, std::max<size_t>(u->n_pieces, 1));
+	const int T = (int)std::min<size_t>((size_t)h->osw.h2d_threads, std::max<size_t>(u->n_pieces, 1));
 	uint8_t* const dst = h->d_comp.p; const uint8_t* const src = bytes + beg; const int device = h->device;
-	int delay_us = 0; if (const char* e = getenv("NGSQC_H2D_DELAY_US")) delay_us = std::max(0, atoi(e));   // (tests: a slow link, so that the chunk stream really waits for pieces)
+	const int delay_us = h->osw.h2d_delay_us;   // (tests: a slow link, so that the chunk stream really waits for pieces)
 	for (int t = 0; t < T && u->n_pieces; ++t)
-		u->th.emplace_back([u, dst, src, device, delay_us] {
+		u->th.emplace_back([u, dst, src, device, delay_us, dbg] {
 			hipStream_t st = nullptr;
 			try
 			{
@@ -337,7 +298,7 @@ void upload_start(ngsqc_handle* h, const uint8_t* bytes, size_t beg, size_t end)
 			}
 			catch (std::exception& e) { std::lock_guard<std::mutex> g(u->mu); if (u->err.empty()) u->err = e.what(); u->cv.notify_all(); }
 			if (st) (void)hipStreamDestroy(st);
-			{ std::lock_guard<std::mutex> g(u->mu); if (++u->done == u->th.size()) { u->t_done = wall_ms(); dbg_stamp("upload: last piece on the device"); } }
+			{ std::lock_guard<std::mutex> g(u->mu); if (++u->done == u->th.size()) { u->t_done = wall_ms(); dbg_stamp(dbg, "upload: last piece on the device"); } }
 			u->cv.notify_all();
 		});
 }
@@ -375,9 +336,8 @@ void stream_pass_begin(ngsqc_handle* h)
 	while (u->ev.size() < u->sp.size()) { hipEvent_t e; HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming)); u->ev.push_back(e); }
 	u->recorded.assign(u->sp.size(), 0); u->next = 0; u->done = 0; u->p2_enq = 0; u->err.clear(); u->t0 = wall_ms(); u->t_done = u->t0;
 	for (size_t& w : u->waited) w = 0;
-	int T = 4; if (const char* e = getenv("NGSQC_H2D_THREADS")) T = std::max(1, atoi(e));
-	T = (int)std::min<size_t>((size_t)T, u->sp.size());
-	int delay_us = 0; if (const char* e = getenv("NGSQC_H2D_DELAY_US")) delay_us = std::max(0, atoi(e));
+	const int T = (int)std::min<size_t>((size_t)h->osw.h2d_threads, u->sp.size());
+	const int delay_us = h->osw.h2d_delay_us;
 	uint8_t* const dst = h->d_comp.p; const int device = h->device; const int slots = h->comp_slots; hipEvent_t* const ev_chunk = h->ev_chunk.data();
 	// The source of a piece is the mapping of the file (hipMemcpyAsync stages a pageable source through the runtime's pinned buffers). Reading through the mapping
 	// faults in one page-table entry per 4 KB - 15 M of them for a 60 GB file - and tearing them down again costs 0.3 - 0.75 s at close for a 19 GB file. Measured
@@ -456,8 +416,6 @@ void upload_finish(ngsqc_handle* h)
 	h->tm.h2d_ms = u->t_done - u->t0;
 }
 
-constexpr int64_t SHARD_TAIL_MEMBERS = 64;   // members behind a shard that are inflated to complete its last record (NGSQC_SHARD_TAIL_MEMBERS)
-
 void open_common(ngsqc_handle* h, const uint8_t* bytes, size_t n, int device, int shard, int n_shards)
 {
 	if (n_shards < 1 || shard < 0 || shard >= n_shards) throw ArgError("invalid shard index");
@@ -466,23 +424,20 @@ void open_common(ngsqc_handle* h, const uint8_t* bytes, size_t n, int device, in
 	{
 		// a path: the copy starts before anything else looks at the file (the BGZF member walk below runs beside it; the header read waits for the first pieces only)
 		if (n >= 4 && memcmp(bytes, "CRAM", 4) == 0) throw std::domain_error("a CRAM file has no BGZF members: ngsqc_open / ngsqc_open_memory decode it (cram.hip)");
-		dbg_stamp("open: start");
+		dbg_stamp(h->osw.debug, "open: start");
 		init_device(h, device);
-		dbg_stamp("open: device and streams ready");
+		dbg_stamp(h->osw.debug, "open: device and streams ready");
 		// A large file is STREAMED (round 4): no 60 GB image buffer (its allocation alone took as long as the copy, and a BAM no longer has to fit HBM next to its
 		// tiles) - every job copies the file through a ring of K1-chunk slots. NGSQC_STREAM_IMAGE=1 / 0 forces / forbids it, NGSQC_STREAM_IMAGE_MIN_MB moves the
 		// threshold (default 4096: smaller files stay resident, so repeated jobs on them do not cross PCIe again).
-		{
-			const char* es = getenv("NGSQC_STREAM_IMAGE"); size_t min_mb = 4096; if (const char* em = getenv("NGSQC_STREAM_IMAGE_MIN_MB")) min_mb = (size_t)std::max(0, atoi(em));
-			h->stream_img = es ? atoi(es) != 0 : (n >> 20) >= min_mb;
-		}
+		h->stream_img = h->osw.stream_image != SW_UNSET ? h->osw.stream_image != 0 : (n >> 20) >= (size_t)h->osw.stream_image_min_mb;
 		h->up->src_base = bytes; h->up->map_n = n;
 		if (!h->stream_img) upload_start(h, bytes, 0, n);
-		dbg_stamp("open: upload threads started");
-		scan_bgzf(bytes, n, h->blocks, h->crc, h->total, n_shards == 1 ? &h->member_off : nullptr);
-		dbg_stamp("open: BGZF member table walked");
+		dbg_stamp(h->osw.debug, "open: upload threads started");
+		scan_bgzf(bytes, n, h->blocks, h->crc, h->total, n_shards == 1 ? &h->member_off : nullptr, h->osw.walk_threads);   // (in pieces since round 4: the first job races the copy, tests/test_gpu_tools.py)
+		dbg_stamp(h->osw.debug, "open: BGZF member table walked");
 	}
-	else { scan_bgzf(bytes, n, h->blocks, h->crc, h->total, n_shards == 1 ? &h->member_off : nullptr); init_device(h, device); }
+	else { scan_bgzf(bytes, n, h->blocks, h->crc, h->total, n_shards == 1 ? &h->member_off : nullptr, h->osw.walk_threads); init_device(h, device); }
 	Timer t(h->stream); t.start();
 	h->shard = shard; h->n_shards = n_shards;
 	if (n_shards == 1)
@@ -490,7 +445,7 @@ void open_common(ngsqc_handle* h, const uint8_t* bytes, size_t n, int device, in
 		if (!h->up) { upload_compressed(h, bytes, 0, n); h->tm.h2d_ms = t.stop(); }
 		h->tm.compressed_bytes = (int64_t)n; h->tm.inflated_bytes = h->total;
 		read_header(h, (int64_t)h->blocks.size());
-		dbg_stamp("open: BAM header read");
+		dbg_stamp(h->osw.debug, "open: BAM header read");
 		return;
 	}
 	// ---- header: only the first members are sent to the device ----
@@ -512,7 +467,7 @@ void open_common(ngsqc_handle* h, const uint8_t* bytes, size_t n, int device, in
 		return lo;
 	};
 	const int64_t m0 = first_member_at(shard), m1 = first_member_at(shard + 1);
-	int64_t tail = SHARD_TAIL_MEMBERS; if (const char* e = getenv("NGSQC_SHARD_TAIL_MEMBERS")) tail = std::max<int64_t>(0, atoll(e));
+	const int64_t tail = h->osw.shard_tail_members;   // members behind a shard that are inflated to complete its last record
 	const int64_t m_end = std::min<int64_t>(nb, m1 + (m1 > m0 ? tail : 0));
 	std::vector<BlockDesc> own; std::vector<uint32_t> own_crc;
 	size_t cbeg = 0, cend = 0; int64_t u0 = 0, u_own = 0, u_all = 0;
@@ -537,8 +492,8 @@ void open_common(ngsqc_handle* h, const uint8_t* bytes, size_t n, int device, in
 }
 
 // ---- layout of the tile stream: K1 chunks, tiles (whole chunks), token ring, static device tables -------------------------
-// NGSQC_TILE_MEMBERS=k (tests): chunks and tiles of k members. NGSQC_TILE_CHUNKS: chunks per tile (default 2).
-// NGSQC_K1_CHUNK_DIV: chunk = one decoder round / div. NGSQC_CARRY_MAX: bytes reserved in front of a tile for a straddling record.
+// Everything here comes from the handle's OpenSwitches (this runs in ngsqc_open's layout thread): NGSQC_TILE_MEMBERS=k (tests): chunks and tiles of k members.
+// NGSQC_TILE_CHUNKS: chunks per tile (default 8, 1 for a streamed image). NGSQC_CARRY_MAX: bytes reserved in front of a tile for a straddling record.
 void plan_layout_now(ngsqc_handle* h, bool early_pass = false)
 {
 	if (h->planned) return;
@@ -546,26 +501,23 @@ void plan_layout_now(ngsqc_handle* h, bool early_pass = false)
 	const int64_t nb = (int64_t)h->blocks.size();
 	h->planned = true;
 	if (nb == 0) return;
-	int64_t div = 1; if (const char* e = getenv("NGSQC_K1_CHUNK_DIV")) div = std::max<int64_t>(1, atoll(e));
-	const int64_t mul = 1;
 	// A streamed image is bound by PCIe (60 GB in 1.2 s against 0.57 s of K1), and what a one-shot tool waits for besides the copy is the ALLOCATION of the stream's
 	// buffers (28 GB/s when another process has just given the memory back): half-size chunks and one chunk per tile cut the ring, the token pool and the tile
 	// buffers from 65 GB to 23 GB for the 30x file; the job stays behind the copy
-	if (h->stream_img && !getenv("NGSQC_K1_CHUNK_DIV")) div = 2;
-	const int64_t cw = getenv("NGSQC_K1_CHUNK_WAVES") ? std::max(1, atoi(getenv("NGSQC_K1_CHUNK_WAVES"))) : K1_CHUNK_WAVES_PER_CU;   // (dev: chunk size in decoder waves per CU)
-	const int64_t lanes = std::max<int64_t>(64, (int64_t)h->n_cu * cw * 64 * mul / div);
+	const int64_t div = h->stream_img ? 2 : 1;   // (chunk = one decoder round / div)
+	const int64_t lanes = std::max<int64_t>(64, (int64_t)h->n_cu * K1_CHUNK_WAVES_PER_CU * 64 / div);
 	// two K1 chunks per tile (192 M reads, 12 chunks; job Mreads/s | un-pipelined scan-stage share of the HBM roofline): 1 chunk 919 | 0.36, 2 chunks 931-941 | 0.43-0.44, 4 chunks
 	// 930 | 0.46. The job barely cares; the chain walk of the fused scan has one thread per MEMBER, so a tile of 195 k members keeps twice the lines in flight of a 97 k one.
 	// (round 6: four chunks of 5 waves per CU; 17 -> 10 tiles of the 30x file, the full-size step 451 -> 446 (three chunks) -> 443 ms: fewer tile boundaries, where the chunk stream runs thin)
 	// (round 6, with the decoder at three waves per SIMD: EIGHT chunks per tile - as many as fit the HBM beside the image of the 30x file, the memory bound below - and eight token slots;
 	// 5 tiles of the 30x file. Chunks per tile | full-size step: 4 | 433 ms, 5 | 427-429, 6 | 424, 7 | 422, 8 | 414.6 (K1 wall 405 -> 370 ms: the chunk stream runs thin at every tile
 	// boundary), profiles/r06_schedule_probe.txt. A tile of eight chunks is 655 360 walkers = exactly two rounds of the coverage tools' walk)
-	int64_t cpt = h->stream_img ? 1 : 8; if (const char* e = getenv("NGSQC_TILE_CHUNKS")) cpt = std::max<int64_t>(1, atoll(e));
+	int64_t cpt = h->osw.tile_chunks ? h->osw.tile_chunks : h->stream_img ? 1 : 8;
 	// Three tile buffers: K1 of tile t+2 is queued before the host waits for tile t, so the decoder waves never run out of queued work while the
 	// host reads back K2 / consumer results of tile t (with two buffers the queue ran dry for ~6 ms per tile).
 	h->nbuf = 3;
-	bool forced = false;
-	if (const char* e = getenv("NGSQC_TILE_MEMBERS")) { h->chunk = std::max<int64_t>(1, atoll(e)); cpt = 1; forced = true; }
+	const bool forced = h->osw.tile_members > 0;
+	if (forced) { h->chunk = h->osw.tile_members; cpt = 1; }
 	else
 	{
 		const int64_t nch0 = std::max<int64_t>(1, (nb + lanes - 1) / lanes);
@@ -575,7 +527,7 @@ void plan_layout_now(ngsqc_handle* h, bool early_pass = false)
 	// token pool of a chunk slot: the pages the chunk with the largest need may take (k1_types.h), queue order inside every chunk
 	std::vector<uint32_t> ord((size_t)nb);
 	std::vector<int64_t> chunk_bytes((size_t)h->nch, 0);
-	double pool_factor = 1.0; if (const char* e = getenv("NGSQC_TOKEN_POOL_FACTOR")) pool_factor = std::max(0.01, atof(e));   // (tests: a small pool forces the second-chance path)
+	const double pool_factor = h->osw.token_pool_factor;   // (tests: a small pool forces the second-chance path)
 	h->slot_pages = 0;
 	for (int64_t c = 0; c < h->nch; ++c)
 	{
@@ -590,10 +542,9 @@ void plan_layout_now(ngsqc_handle* h, bool early_pass = false)
 	// the kernels address a literal table by a 32-bit WORD offset into the slot (page * K1_PAGE_WORDS): a slot never holds 2^22 pages or more (16 GiB; poorly
 	// compressible payloads could ask for that) - members that then find the pool used up take the second-chance path like any other overflow
 	h->slot_pages = std::min<int64_t>(h->slot_pages, (1ll << 22) - 1);
-	h->k1_slots = K1_SLOTS_DEFAULT; if (const char* e = getenv("NGSQC_TOKEN_SLOTS")) h->k1_slots = std::min(8, std::max(2, atoi(e)));
 	const int64_t n_slots = std::min<int64_t>(h->k1_slots, h->nch);
 	// tiles: as many chunks as fit the tile buffers next to the ring (at most cpt)
-	int64_t carry_max = 64ll << 20; if (const char* e = getenv("NGSQC_CARRY_MAX")) carry_max = std::max<int64_t>(0, atoll(e));
+	const int64_t carry_max = h->osw.carry_max;
 	if (!forced && h->nch > 1)
 	{
 		size_t free_b = 0, total_b = 0;
@@ -629,7 +580,7 @@ void plan_layout_now(ngsqc_handle* h, bool early_pass = false)
 	if (h->stream_img)
 	{
 		// ring of chunk slots: chunk c's bytes [lo_c, hi_c + 64) go to slot c % slots; a member's cpos becomes its place in that slot (static: d_kdesc is built once)
-		h->comp_slots = (int)std::min<int64_t>(8, h->nch);   // (eight half-size chunks = 7.6 GB of the 30x file: the copy runs well ahead of K1, so the host rarely blocks on a piece) if (const char* e = getenv("NGSQC_COMP_SLOTS")) h->comp_slots = (int)std::min<int64_t>(h->nch, std::max(2, atoi(e)));
+		h->comp_slots = (int)std::min<int64_t>(h->osw.comp_slots ? h->osw.comp_slots : 8, h->nch);   // (eight half-size chunks = 7.6 GB of the 30x file: the copy runs well ahead of K1, so the host rarely blocks on a piece)
 		h->chunk_lo.assign((size_t)h->nch, 0); std::vector<uint64_t> chunk_hi((size_t)h->nch, 0); size_t slot = 0;
 		for (int64_t c = 0; c < h->nch; ++c)
 		{
@@ -641,7 +592,7 @@ void plan_layout_now(ngsqc_handle* h, bool early_pass = false)
 		h->comp_slot_bytes = (slot + 1024 + 4095) & ~(size_t)4095;
 		h->d_comp.alloc((size_t)h->comp_slots * h->comp_slot_bytes + 1024);
 		HIPCHK(hipMemsetAsync(h->d_comp.p, 0, (size_t)h->comp_slots * h->comp_slot_bytes + 1024, h->stream));   // (the bytes behind a slot's last payload are read as padding)
-		size_t piece = 64u << 20; if (const char* e = getenv("NGSQC_H2D_PIECE_MB")) piece = (size_t)std::max(1, atoi(e)) << 20;
+		const size_t piece = (size_t)h->osw.h2d_piece_mb << 20;
 		ngsqc_handle::Upload* u = h->up; u->sp.clear(); u->chunk_first.assign((size_t)h->nch + 1, 0);
 		for (int64_t c = 0; c < h->nch; ++c)
 		{
@@ -656,11 +607,11 @@ void plan_layout_now(ngsqc_handle* h, bool early_pass = false)
 	}
 	h->d_kdesc.upload(kd, h->stream); h->d_order.upload(ord, h->stream); h->d_crc.upload(h->crc, h->stream);
 	h->d_tok_cnt.ensure((size_t)nb + 8); h->d_tok_first.ensure((size_t)nb + 8); h->d_status.ensure((size_t)nb); h->d_work.ensure((size_t)h->nch); h->d_pool_ctr.ensure((size_t)h->nch);
-	dbg_stamp("layout: member tables on the device");
+	dbg_stamp(h->osw.debug, "layout: member tables on the device");
 	h->d_tok.ensure((size_t)(n_slots * h->slot_pages) * K1_PAGE_WORDS + 16);
-	dbg_stamp("layout: token pool allocated");
+	dbg_stamp(h->osw.debug, "layout: token pool allocated");
 	for (int i = 0; i < std::min(nt, h->nbuf); ++i) h->buf[i].ensure((size_t)(h->pfx + h->max_tile_bytes) + 64);
-	dbg_stamp("layout: tile buffers allocated");
+	dbg_stamp(h->osw.debug, "layout: tile buffers allocated");
 	h->max_tile_members = 0; for (auto& tl : h->tiles) h->max_tile_members = std::max(h->max_tile_members, tl.second);
 	h->p_status.ensure((size_t)nb);
 	while ((int64_t)h->ev_chunk.size() < 4 * h->nch) { hipEvent_t e; HIPCHK(hipEventCreate(&e)); h->ev_chunk.push_back(e); }
@@ -669,7 +620,7 @@ void plan_layout_now(ngsqc_handle* h, bool early_pass = false)
 	HIPCHK(hipStreamSynchronize(h->stream));   // the host vectors above go out of scope
 	h->tm.n_tiles = nt;
 	if (h->stream_img && early_pass) { stream_pass_begin(h); h->up->pass_fresh = true; }   // (ngsqc_open's layout thread: the copy starts now)
-	if (getenv("NGSQC_DEBUG")) fprintf(stderr, "[ngsqc] layout: %d tiles, %lld chunks, token pool %.1f GB, tile buffers %.1f GB, %.1f ms\n", nt, (long long)h->nch, (double)n_slots * (double)h->slot_pages * K1_PAGE_WORDS * 4e-9, (double)std::min(nt, h->nbuf) * (double)(h->pfx + h->max_tile_bytes) * 1e-9, wall_ms() - pl0);
+	if (h->osw.debug) fprintf(stderr, "[ngsqc] layout: %d tiles, %lld chunks, %d image slots, token pool %.1f GB, tile buffers %.1f GB, %.1f ms\n", nt, (long long)h->nch, h->comp_slots, (double)n_slots * (double)h->slot_pages * K1_PAGE_WORDS * 4e-9, (double)std::min(nt, h->nbuf) * (double)(h->pfx + h->max_tile_bytes) * 1e-9, wall_ms() - pl0);
 }
 
 void plan_layout(ngsqc_handle* h)
@@ -730,7 +681,7 @@ void open_range_common(ngsqc_handle* h, const uint8_t* bytes, size_t n, int devi
 			end = (uint64_t)o3 << 16;
 			// a writer that does not keep records inside one BGZF member (htslib does, bam_write1's bgzf_flush_try; others do not) may cut a record at that boundary:
 			// like a shard, the handle takes members behind its own ones to complete it
-			int64_t tail = SHARD_TAIL_MEMBERS; if (const char* e = getenv("NGSQC_SHARD_TAIL_MEMBERS")) tail = std::max<int64_t>(0, atoll(e));
+			const int64_t tail = h->osw.shard_tail_members;
 			if (o3 < n && tail > 0) { own_end = end; walk_bgzf(bytes, n, o3, n, tail, u3, tb, tc); end = (uint64_t)o3 << 16; if (end == own_end) own_end = 0; }
 		}
 	}
@@ -820,10 +771,9 @@ int open_impl(ngsqc_handle** out, const char* path, const void* bytes, size_t n,
 			if (range && range->head_members > 0) sel.max_slices = std::max<int64_t>(2, range->head_members / 4);   // (a slice holds ~10 000 records, a BGZF member ~250: every longer head BamReader::info asks for - x4 each time - brings more slices)
 			// the quality arrays (rANS blocks, about half of the records' bytes) stay compressed and are decoded on the device into the uploaded image (cram_dev.hip):
 			// whole-file handles only (a shard uploads a part of the image); NGSQC_CRAM_DEVICE_QUALS=0 keeps them on the host
-			const char* eq = getenv("NGSQC_CRAM_DEVICE_QUALS");
-			const bool dev_quals = n_shards == 1 && (!eq || atoi(eq) != 0);
+			const bool dev_quals = n_shards == 1 && h->osw.cram_device_quals;
 			cram_src = (const uint8_t*)bytes;
-			const int crc = cram_to_bam_image((const uint8_t*)bytes, n, h->path, cram_image, err, &sel, dev_quals ? &qplan : nullptr);
+			const int crc = cram_to_bam_image((const uint8_t*)bytes, n, h->path, cram_image, err, h->osw, &sel, dev_quals ? &qplan : nullptr);
 			if (crc == NGSQC_E_FORMAT) throw FormatError(err);
 			if (crc == NGSQC_E_IO) throw IoError(err);
 			if (crc == NGSQC_E_UNSUPPORTED) throw std::domain_error(err);
@@ -831,21 +781,19 @@ int open_impl(ngsqc_handle** out, const char* path, const void* bytes, size_t n,
 			bytes = cram_image.data(); n = cram_image.size(); h->from_cram = true;
 			range = nullptr;   // (regions, a record range, the first records: the whole file holds them)
 		}
-		const char* ea = getenv("NGSQC_ASYNC_H2D");
-		if (path && !from_cram && n_shards == 1 && !range && (!ea || atoi(ea) != 0)) h->up = new ngsqc_handle::Upload();
+		if (path && !from_cram && n_shards == 1 && !range && h->osw.async_h2d) h->up = new ngsqc_handle::Upload();
 		if (range) open_range_common(h, (const uint8_t*)bytes, n, device, *range); else open_common(h, (const uint8_t*)bytes, n, device, shard, n_shards);
 		if (from_cram && !qplan.jobs.empty())
 		{
 			// (the BGZF wrapper of the image is our own and its CRC-32s were taken over blank qualities; every CRAM block was CRC-checked on the host)
 			h->verify_crc = false;
 			const double ms = cram_device_quals(cram_src, qplan, h->d_comp.p, cram_image.size(), h->stream);
-			if (getenv("NGSQC_TIMING")) fprintf(stderr, "[ngsqc] cram: %zu quality blocks (%llu bytes, %zu records) decoded on the device in %.3f ms\n", qplan.jobs.size(), (unsigned long long)qplan.out_bytes, qplan.patches.size(), ms);
+			if (h->osw.timing) fprintf(stderr, "[ngsqc] cram: %zu quality blocks (%llu bytes, %zu records) decoded on the device in %.3f ms\n", qplan.jobs.size(), (unsigned long long)qplan.out_bytes, qplan.patches.size(), ms);
 		}
 		if (h->up) { h->up->map = map; h->up->map_n = map_n; h->up->fd = fd; map = nullptr; fd = -1; }   // the mapping lives until the last piece is copied
-		const char* ep = getenv("NGSQC_ASYNC_PLAN");
-		if (h->up && (!ep || atoi(ep) != 0))
+		if (h->up && h->osw.async_plan)
 			h->plan_thread = std::thread([h] {
-				try { HIPCHK(hipSetDevice(h->device)); dbg_stamp("layout thread: start"); plan_layout_now(h, true); dbg_stamp("layout thread: done"); }
+				try { HIPCHK(hipSetDevice(h->device)); dbg_stamp(h->osw.debug, "layout thread: start"); plan_layout_now(h, true); dbg_stamp(h->osw.debug, "layout thread: done"); }
 				catch (std::exception& e) { h->plan_err = e.what(); h->planned = false; }
 			});
 	}

@@ -317,7 +317,7 @@ void launch_index_guess(const uint8_t* d_infl, int64_t total, const BlockDesc* d
 	if (n <= 0) return;
 	// (Round 5 first tried sixteen waves per group of members, each looking through a contiguous sixteenth to its end: 6.6 ms against the wave-per-entry kernel's 1.6 ms
 	// per tile of the ONT-like shard, profiles/r05_scan_probe.txt - removed. Interleaved stripes with a common end of the round are the form that is kept.)
-	const char* e = getenv("NGSQC_GUESS_WAVES"); const int waves = e ? atoi(e) : (ksh <= -3 ? 8 : ksh < 0 ? 4 : 1);   // groups of members (long reads): a workgroup per entry - eight waves for groups of 8 and more (0.50 vs 0.69 ms at 16), four below (0.84 vs 1.06 ms at 4); 1: a wave per entry
+	const int waves = ksh <= -3 ? 8 : ksh < 0 ? 4 : 1;   // groups of members (long reads): a workgroup per entry - eight waves for groups of 8 and more (0.50 vs 0.69 ms at 16), four below (0.84 vs 1.06 ms at 4); 1: a wave per entry
 	if (waves == 4 || waves == 8)
 	{
 		const dim3 grid((unsigned)(n < 65536 ? n : 65536));

@@ -82,7 +82,7 @@ struct ScanState : ngsqc_handle::FusedScan
 		// (opt-in, NGSQC_BASEQ_RIDE=1: on the bench's data - four quality levels, half of all bases below 20 - the mask is 75 atomic pairs per record, and the compacted
 		// list concentrates them on neighbouring addresses: 10.1 ms of kernels per 48 M reads against 6.2 for K2 + the thread-per-record scan, profiles/r05_scan_probe.txt;
 		// with instrument qualities - a few per cent below 20 - the walk's index time, 0.3 against 2.6 ms, is what is left)
-		{ const char* e = getenv("NGSQC_BASEQ_RIDE"); bq_ride = sp.mode == MODE_DEPTH && sp.min_baseq > 0 && !(e && atoi(e) == 0); } if (bq_ride) d_bq_count.ensure(1);   // (round 6: on by default - the list's decrements are aggregated in LDS tiles, baseq_tile_kernel; NGSQC_BASEQ_RIDE=0: K2 + the thread-per-record scan)
+		bq_ride = sp.mode == MODE_DEPTH && sp.min_baseq > 0 && h->sw.baseq_ride; if (bq_ride) d_bq_count.ensure(1);   // (round 6: on by default - the list's decrements are aggregated in LDS tiles, baseq_tile_kernel; NGSQC_BASEQ_RIDE=0: K2 + the thread-per-record scan)
 		bq_min = 0;
 		sp.bq_list = nullptr; sp.bq_count = nullptr; sp.bq_cap = 0;
 		run_max = 0; paired_seen = false; sum_runmax = 0; fix_len = 0; prev_total = 0; prev_usable = 0; best_key = 0; first_paired = ~0ull;
@@ -97,7 +97,7 @@ struct ScanState : ngsqc_handle::FusedScan
 		{
 			if (sgn > 0) { d_bq.ensure_slack(std::max((size_t)std::max<int64_t>(total / 2048, 1 << 16), bq_min)); HIPCHK(hipMemsetAsync(d_bq_count.p, 0, sizeof(unsigned long long), h->stream)); }   // (one record in fifty overlaps an exome: 340 bytes x 50 = a list entry per 17 KB; sized for one per 2 KB, checked by index_tile)
 			sp.bq_list = d_bq.p; sp.bq_count = d_bq_count.p; sp.bq_cap = (int64_t)d_bq.n;
-			if (const char* e = getenv("NGSQC_BQ_LIST_CAP")) sp.bq_cap = std::min<int64_t>(sp.bq_cap, std::max<int64_t>(1, atoll(e)));   // (tests: a list that overflows)
+			if (h->sw.bq_list_cap) sp.bq_cap = std::min(sp.bq_cap, h->sw.bq_list_cap);   // (tests: a list that overflows)
 		}
 		if (sgn > 0)
 		{
@@ -107,7 +107,7 @@ struct ScanState : ngsqc_handle::FusedScan
 			HIPCHK(hipMemcpyAsync(d_counters.p + A_TILE_KEY, s, 2 * sizeof(unsigned long long), hipMemcpyHostToDevice, h->stream));   // A_TILE_KEY, A_TILE_PAIRED
 		}
 		const size_t iv = h->evlog->begin(h->stream, &kernel_ms, &stage_ms);   // (the walk + scan kernel: booked as scan time, not under K2)
-		launch_walk_scan(sp, d_desc, ne, prefix, ksh, nm, h->d_start.p, h->d_cnt.p, h->d_next.p, h->d_bad.p, h->d_rel.p, h->stream);
+		launch_walk_scan(sp, d_desc, ne, prefix, ksh, nm, h->d_start.p, h->d_cnt.p, h->d_next.p, h->d_bad.p, h->d_rel.p, h->sw.walk_waves, h->stream);
 		h->evlog->end(iv, h->stream); launches++;
 		sp.sgn = 1; sp.scan_limit = INT64_MAX;
 	}
@@ -260,7 +260,7 @@ struct PileupState
 	static constexpr int64_t CAND_CAP = 4ll << 20;
 	void attach(ScanParams& sp, const ngsqc_handle::FusedScan* scan)
 	{
-		if (n_sites == 0 || getenv("NGSQC_NO_FUSED_PILEUP")) return;
+		if (n_sites == 0) return;
 		d_cand.ensure((size_t)CAND_CAP); d_ncand.ensure(1);
 		sp.pile.site_pos = d_pos.p; sp.pile.tid_first = d_tf.p; sp.pile.tid_last = d_tl.p; sp.pile.bucket = d_bucket.p; sp.pile.tid_bucket0 = d_tb0.p;
 		sp.pile.list = d_cand.p; sp.pile.count = d_ncand.p; sp.pile.cap = CAND_CAP; sp.pile.min_mapq = min_mapq; sp.pile.include_npp = include_npp;
@@ -485,7 +485,7 @@ void write_bai(ngsqc_handle* h, const char* out_path, bool csi, int min_shift)
 	HIPCHK(hipMemsetAsync(d_small.p, 0, 16, h->stream));   // [0] runs of the tile, [1] flags
 	HIPCHK(hipStreamSynchronize(h->stream));
 	std::vector<BaiRun> runs; std::vector<BaiRun> part;
-	const bool dbg = getenv("NGSQC_DEBUG") != nullptr;
+	const bool dbg = h->sw.debug;
 	if (dbg) fprintf(stderr, "[bai] n_ref %d, windows %lld\n", n_ref, (long long)n_win);
 	stream_tiles(h, [&](const TileCtx& c) {
 		if (dbg) fprintf(stderr, "[bai] tile %d: %lld records, u_base %lld\n", c.tile, (long long)c.n_rec, (long long)(h->tile_u_lo - h->tile_prefix));
@@ -662,7 +662,7 @@ void run_job(ngsqc_handle* h, const ngsqc_job_desc* j, ngsqc_job_result* r, ngsq
 	if (do_reads && !r->read_stats) throw ArgError("raw-read QC job without a result buffer");
 	if (j->n_sites < 0) throw ArgError("invalid site count");
 	const double w0 = wall_ms();
-	dbg_stamp("job: start");
+	dbg_stamp(h->sw.debug, "job: start");
 	h->tm.scan_ms = 0; h->tm.scan_kernel_ms = 0; h->tm.scan_launches = 0; h->tm.finalize_ms = 0; h->tm.depth_scan_ms = 0; h->tm.pileup_ms = 0; h->tm.reads_ms = 0; h->tm.scan_algorithmic_bytes = 0;   // (every per-consumer field of the previous job)
 	Timer total(h->stream); total.start();
 	ngsqc_handle::Partial local_map; ScanState dscan; PileupState pile; IndelState indel; ReadsState reads;
@@ -671,17 +671,17 @@ void run_job(ngsqc_handle* h, const ngsqc_job_desc* j, ngsqc_job_result* r, ngsq
 	if (do_map) { mapping_setup(h, j->mapping, map); map.scan.in_pass_fix = !part; map.scan.begin(h); }
 	if (do_depth) { depth_setup(h, j->depth, h->ds[1], dscan); dscan.in_pass_fix = false; dscan.begin(h); }
 	if (do_sites) pile.begin(h, j->sites, j->n_sites, j->site_min_mapq, j->site_min_baseq, j->site_include_npp);
-	if (do_sites && do_map) pile.attach(map.scan.sp, &map.scan);   // (the pileup's candidates come from the scan that rides K2's chain walk)
+	if (do_sites && do_map && !h->sw.no_fused_pileup) pile.attach(map.scan.sp, &map.scan);   // (the pileup's candidates come from the scan that rides K2's chain walk)
 	if (do_indel) indel.begin(h, ij->windows, ij->n, ij->include_npp);
 	if (do_reads) reads.begin(h, j->read_qc_single_end);
 	const double w1 = wall_ms();
-	const bool depth_rides = do_depth && (j->depth->min_baseq <= 0 || !(getenv("NGSQC_BASEQ_RIDE") && atoi(getenv("NGSQC_BASEQ_RIDE")) == 0));
+	const bool depth_rides = do_depth && (j->depth->min_baseq <= 0 || h->sw.baseq_ride);
 	FuseGuard fg(h, do_map ? &map.scan : (depth_rides ? &dscan : nullptr));
 	// the record offsets of a tile are only expanded when a consumer reads them: the mapping scan rides the chain walk (deferred long-CIGAR records and the
 	// order-dependent fix-ups ask for them), the site pileup works on the walk's candidate list; the extra depth scan and the raw-read QC read every record
 	struct LazyGuard { ngsqc_handle* h; ~LazyGuard() { h->lazy_recoff = false; } } lg{h};
 	// (round 6: a coverage tool's job - the depth scan alone, riding the walk - does not expand them either: 0.23 ms per tile of the 30x file, 6 % of its scan stage)
-	h->lazy_recoff = !part && !do_reads && !do_indel && ((do_map && !do_depth) || (!do_map && depth_rides && !do_sites)) && !getenv("NGSQC_EAGER_RECOFF");
+	h->lazy_recoff = !part && !do_reads && !do_indel && ((do_map && !do_depth) || (!do_map && depth_rides && !do_sites)) && !h->sw.eager_recoff;
 	stream_tiles(h, [&](const TileCtx& c) {
 		if (do_map) map.scan.tile(h, c);
 		if (part && c.ord_base == 0 && c.n_rec > 0)
@@ -734,7 +734,7 @@ void run_job(ngsqc_handle* h, const ngsqc_job_desc* j, ngsqc_job_result* r, ngsq
 	h->cur_ds = do_map || !do_depth ? 0 : 1;
 	h->tm.total_ms = total.stop();
 	h->tm.job_wall_ms = wall_ms() - w0;
-	if (getenv("NGSQC_DEBUG")) fprintf(stderr, "[ngsqc] job: setup %.2f ms, tile stream %.2f ms (K1 %.2f), results %.2f ms\n", w1 - w0, w2 - w1, h->tm.inflate_ms, wall_ms() - w2);
+	if (h->sw.debug) fprintf(stderr, "[ngsqc] job: setup %.2f ms, tile stream %.2f ms (K1 %.2f), results %.2f ms\n", w1 - w0, w2 - w1, h->tm.inflate_ms, wall_ms() - w2);
 }
 
 DepthSet& cur_depth(ngsqc_handle* h) { return h->ds[h->cur_ds]; }
@@ -1000,7 +1000,7 @@ void depth_scan(ngsqc_handle* h, const ngsqc_depth_params* p, bool finalize)
 	// took the thread-per-record path - K2, then the scan kernel - because the decrements inside the walk stalled its lanes: 147 vs 224 ms per 96 M reads)
 	// (round 6: a riding depth scan does not have the record offsets expanded - deferred long-CIGAR records ask for them (ensure_recoff): 0.23 ms per tile of the 30x file)
 	struct LazyGuard { ngsqc_handle* h; ~LazyGuard() { h->lazy_recoff = false; } } lg{h};
-	{ const char* e = getenv("NGSQC_BASEQ_RIDE"); const bool ride = p->min_baseq <= 0 || !(e && atoi(e) == 0); h->lazy_recoff = ride && finalize && !getenv("NGSQC_EAGER_RECOFF"); FuseGuard fg(h, ride ? &sc : nullptr); stream_tiles(h, [&](const TileCtx& c) { sc.tile(h, c); return true; }); }
+	{ const bool ride = p->min_baseq <= 0 || h->sw.baseq_ride; h->lazy_recoff = ride && finalize && !h->sw.eager_recoff; FuseGuard fg(h, ride ? &sc : nullptr); stream_tiles(h, [&](const TileCtx& c) { sc.tile(h, c); return true; }); }
 	sc.end(h);
 	h->cur_ds = 0;
 	h->tm.scan_ms = sc.stage_ms; h->tm.scan_kernel_ms = sc.kernel_ms; h->tm.scan_launches = sc.launches; h->tm.scan_algorithmic_bytes = (int64_t)sc.dev[A_ALG_BYTES];

@@ -28,13 +28,8 @@ __device__ __forceinline__ uint64_t name_hash(const uint8_t* p, int n)   // FNV-
 	return h;
 }
 
-// test hook NGSQC_NAME_HASH_BITS: fewer hash bits, collisions everywhere
-inline uint64_t name_hash_mask()
-{
-	const char* hb = getenv("NGSQC_NAME_HASH_BITS");
-	const int bits = hb ? std::max(1, std::min(63, atoi(hb))) : 63;
-	return bits >= 63 ? (~0ull >> 1) : ((1ull << bits) - 1);
-}
+// test hook NGSQC_NAME_HASH_BITS (CallSwitches::name_hash_bits, 1 .. 63): fewer hash bits, collisions everywhere
+inline uint64_t name_hash_mask(int bits) { return bits >= 63 ? (~0ull >> 1) : ((1ull << bits) - 1); }
 
 __device__ __forceinline__ bool same_name(const uint8_t* a, const uint8_t* b)
 {
@@ -263,11 +258,7 @@ struct NameJoin
 
 // one output stream in windows of W bytes (NGSQC_WRITE_WINDOW_PIECES: pieces of 0xff00 bytes per window, a test hook; default about 1 GiB): its device and pinned
 // memory does not depend on the size of the file or of a tile
-inline int64_t write_window_bytes()
-{
-	const char* wp = getenv("NGSQC_WRITE_WINDOW_PIECES");
-	return std::max<int64_t>(1, wp ? atoll(wp) : 16384) * BGZF_PIECE;
-}
+inline int64_t write_window_bytes(int64_t pieces) { return pieces * BGZF_PIECE; }
 
 struct BgzfStream
 {

@@ -144,7 +144,7 @@ K1_KERNEL_OCC(64, P1_WAVES_PER_SIMD) void huff_tokens_kernel(const uint8_t* __re
 	K1_SHARED uint32_t lds[P1_LDS_W];
 	const int lane = wv::lane();
 	P1Lds L{lds, lane};
-	wv::set_priority(park_hi >> 8); park_hi &= 255;   // (upper bits: wave priority of the decoder waves, NGSQC_P1_PRIO)
+	wv::set_priority(park_hi >> 8); park_hi &= 255;   // (upper bits: wave priority of the decoder waves - always 0 since the launcher's priority probe is finished)
 	const wv::u32x4* const comp_q = (const wv::u32x4*)comp;
 	uint32_t* const tab = lds + P1_LANE_W * 64;
 	uint32_t* const stage = lds + P1_LANE_W * 64 + P1_TAB_W + lane * (4 * P1_LINE_GROUPS);   // lane-major; a lane's four groups rotated by lane / 4, so that sixteen lanes' 16-byte accesses meet sixteen different bank quads

@@ -155,8 +155,8 @@ void filter_pairs(ngsqc_handle* h, const ngsqc_pair_filter* fp, const char* out_
 {
 	if (!fp || !out_path || !passed || !dropped) throw ArgError("null argument");
 	if (h->selection || h->n_shards != 1 || h->shard_own_members >= 0) throw ArgError("BamFilter needs a handle on the whole file (not a shard, a range or regions)");
-	PairParams p{fp->min_mq, fp->max_mq, fp->max_mm, fp->max_gap, fp->min_dup, fp->max_is, name_hash_mask()};
-	const bool timing = getenv("NGSQC_TIMING") != nullptr;
+	PairParams p{fp->min_mq, fp->max_mq, fp->max_mm, fp->max_gap, fp->min_dup, fp->max_is, name_hash_mask(h->sw.name_hash_bits)};
+	const bool timing = h->sw.timing;
 	hipStream_t s = h->stream;
 	// the header: the input's bytes (magic, l_text, text, n_ref, refs), in members of its own
 	std::vector<uint8_t> hdr;
@@ -164,7 +164,7 @@ void filter_pairs(ngsqc_handle* h, const ngsqc_pair_filter* fp, const char* out_
 	hdr.insert(hdr.end(), {'B', 'A', 'M', 1}); put32((uint32_t)h->header_text.size()); hdr.insert(hdr.end(), h->header_text.begin(), h->header_text.end());
 	put32((uint32_t)h->ref_names.size());
 	for (size_t i = 0; i < h->ref_names.size(); ++i) { put32((uint32_t)h->ref_names[i].size() + 1); hdr.insert(hdr.end(), h->ref_names[i].begin(), h->ref_names[i].end()); hdr.push_back(0); put32((uint32_t)h->ref_lens[i]); }
-	const int64_t W = write_window_bytes();
+	const int64_t W = write_window_bytes(h->sw.write_window_pieces);
 	BgzfStream out("BamFilter", W, -1);
 	out.sink.open(out_path, std::string("Could not open BAM/CRAM file for writing: ") + out_path);
 	NameJoin j("BamFilter", s);

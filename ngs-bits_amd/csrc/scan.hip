@@ -434,12 +434,7 @@ __device__ __forceinline__ void pile_candidate(const ScanParams& p, const RecVie
 		settle_loads();
 	}
 	if (a.pc_next == INT32_MAX || a.pc_next > end1) return;
-#ifdef NGSQC_NO_WAVE_LISTS
-	const unsigned long long k = atomicAdd(p.pile.count, 1ull);
-	if ((long long)k < p.pile.cap) p.pile.list[k] = o;
-#else
 	wave_list_append(wl, p.pile.list, p.pile.count, p.pile.cap, (unsigned long long)o);
-#endif
 }
 
 template <int MODE>
@@ -777,10 +772,8 @@ __global__ __launch_bounds__(64, WAVES) void walk_scan_kernel(const ScanParams p
                                                         uint32_t* __restrict__ bad, uint16_t* __restrict__ rel)
 {
 	__shared__ uint32_t lds_hist[1002];   // (1000, 1001: the wave's block of the min_baseq list, bq_append)
-#ifndef NGSQC_NO_WAVE_LISTS
 	__shared__ WaveList wl_long, wl_pile;
 	if (threadIdx.x == 0) { wl_long.n = 0; wl_pile.n = 0; }
-#endif
 	if (threadIdx.x < 2) lds_hist[1000 + threadIdx.x] = 0;
 	for (int i = threadIdx.x; i < 1000; i += blockDim.x) lds_hist[i] = 0;
 	__syncthreads();
@@ -827,13 +820,8 @@ __global__ __launch_bounds__(64, WAVES) void walk_scan_kernel(const ScanParams p
 					const long long name = (long long)((b << NAME_SHIFT) | (int64_t)n);
 					long long ref_len = 0;
 					const bool scanned = scan_record<MODE>(p, r, name, a, lds_hist, &ref_len, c4);
-#ifdef NGSQC_NO_WAVE_LISTS
-					if (!scanned && p.sgn > 0) { unsigned long long k = atomicAdd(&p.counters[A_LONG_COUNT], 1ull); if ((long long)k < p.long_cap) p.long_list[k] = name; }
-					if (p.pile.list && p.sgn > 0) pile_candidate(p, r, o, scanned, ref_len, a, nullptr);
-#else
 					if (!scanned && p.sgn > 0) wave_list_append(WAVE_LIST_P(wl_long), p.long_list, &p.counters[A_LONG_COUNT], p.long_cap, (unsigned long long)name);
 					if (p.pile.list && p.sgn > 0) pile_candidate(p, r, o, scanned, ref_len, a, WAVE_LIST_P(wl_pile));
-#endif
 				}
 				++n; o = o_next;
 			}
@@ -848,9 +836,7 @@ __global__ __launch_bounds__(64, WAVES) void walk_scan_kernel(const ScanParams p
 		}
 	}
 	if (MODE == 3 && p.bq_list && p.sgn > 0) bq_close(p, lds_hist + 1000);
-#ifndef NGSQC_NO_WAVE_LISTS
 	if (p.sgn > 0) { wave_list_close(WAVE_LIST_P(wl_long), p.long_list, &p.counters[A_LONG_COUNT], p.long_cap); if (p.pile.list) wave_list_close(WAVE_LIST_P(wl_pile), p.pile.list, p.pile.count, p.pile.cap); }
-#endif
 	flush(p, a, lds_hist);
 }
 
@@ -868,14 +854,14 @@ static void launch_walk_scan_w(const ScanParams& p, const BlockDesc* d_blocks, i
 	}
 	KCHECK();
 }
-// NGSQC_WALK_WAVES = 3 / 4: the register budget the walk is compiled for (waves per SIMD: 170 / 128 VGPRs)
-void launch_walk_scan(const ScanParams& p, const BlockDesc* d_blocks, int64_t n_entries, int64_t prefix, int ksh, int64_t nm, int32_t* d_start, uint32_t* d_cnt, int64_t* d_next_abs, uint32_t* d_bad, uint16_t* d_rel, hipStream_t s)
+// waves (NGSQC_WALK_WAVES) = 3 / 4: the register budget the walk is compiled for (waves per SIMD: 170 / 128 VGPRs); SW_UNSET: by the mode
+void launch_walk_scan(const ScanParams& p, const BlockDesc* d_blocks, int64_t n_entries, int64_t prefix, int ksh, int64_t nm, int32_t* d_start, uint32_t* d_cnt, int64_t* d_next_abs, uint32_t* d_bad, uint16_t* d_rel, int waves, hipStream_t s)
 {
 	if (n_entries <= 0) return;
 	// MODE_DEPTH (the coverage tools) is compiled for FIVE waves per SIMD (95 VGPRs, no scratch): 5 x 4 SIMDs x 256 CUs x 64 lanes = 327 680 walkers are resident at once,
 	// which is exactly a tile of four K1 chunks - with the 99 VGPRs of the budget of three (four resident waves, 262 144 walkers) a tile of the 30x file took a second,
 	// 23 % full round of workgroups: scan kernels 30.7 ms per step with 17 tiles, 34.9 ms with the 10 tiles the K1 schedule wants (profiles/r06_bench_full_30x.json)
-	int waves = p.mode == 3 ? 5 : 3; if (const char* e = getenv("NGSQC_WALK_WAVES")) waves = atoi(e);
+	if (waves == SW_UNSET) waves = p.mode == 3 ? 5 : 3;
 	if (waves >= 5 && p.mode == 3) { const int grid = (int)((n_entries + 63) / 64); hipLaunchKernelGGL((walk_scan_kernel<3, 5>), dim3(grid), dim3(64), 0, s, p, d_blocks, n_entries, prefix, ksh, nm, d_start, d_cnt, d_next_abs, d_bad, d_rel); KCHECK(); }
 	else if (waves >= 4) launch_walk_scan_w<4>(p, d_blocks, n_entries, prefix, ksh, nm, d_start, d_cnt, d_next_abs, d_bad, d_rel, s);
 	else launch_walk_scan_w<3>(p, d_blocks, n_entries, prefix, ksh, nm, d_start, d_cnt, d_next_abs, d_bad, d_rel, s);

@@ -23,7 +23,7 @@ void enqueue_k1_tile(ngsqc_handle* h, int t)
 	uint8_t* out_base = h->buf[t % h->nbuf].p + h->pfx;
 	// CRC of a chunk on its own stream behind the chunk's phase 2, beside phase 2 of the next chunk. With the round-3 kernels (2.4 KB LDS and 37 VGPRs per phase-2 wave) the two no longer compete for a CU's LDS: K1 of a
 	// 96 M-read shard 100 -> 88 ms.
-	const char* eks = getenv("NGSQC_K1_SERIAL"); const bool k1_serial = eks && atoi(eks) != 0;   // profiling: every K1 kernel in line on ONE stream (isolated per-kernel counters)   // 1: the next chunk's phase 1 starts when the whole previous launch is done
+	const bool k1_serial = h->sw.k1_serial;   // profiling: every K1 kernel in line on ONE stream (isolated per-kernel counters)   // 1: the next chunk's phase 1 starts when the whole previous launch is done
 	hipStream_t crc_stream = h->s_crc;
 	// (A "phased" schedule - a tile's decoder launches together, then its phase-2 launches alone - was measured in round 4: 876 against 896 Mreads/s on a 96 M-read
 	// shard, profiles/r04_probe_schedule.txt; removed.)
@@ -31,15 +31,14 @@ void enqueue_k1_tile(ngsqc_handle* h, int t)
 	auto launch_p1 = [&](int64_t c) {
 		const int64_t c0 = c * h->chunk, cn = std::min(h->chunk, nb - c0);
 		hipEvent_t* e4 = &h->ev_chunk[(size_t)(4 * c)];
-		static const int p1_streams = getenv("NGSQC_P1_STREAMS") ? atoi(getenv("NGSQC_P1_STREAMS")) : 2;   // (dev: 1 = one decoder launch at a time)
-		hipStream_t s1 = k1_serial ? h->s_p2 : h->s_p1[p1_streams >= 2 ? (c & 1) : 0];
+		hipStream_t s1 = k1_serial ? h->s_p2 : h->s_p1[c & 1];
 		if (c >= h->k1_slots) HIPCHK(hipStreamWaitEvent(s1, h->ev_chunk[(size_t)(4 * (c - h->k1_slots) + 3)], 0));   // the ring slot is free again
 		if (h->stream_img) stream_wait_chunk(h, c, s1);
 		else if (h->up) { const BlockDesc& lb = h->blocks[(size_t)(c0 + cn - 1)]; upload_wait(h, (size_t)(lb.cpos + lb.clen + 64), s1, k1_serial ? 3 : 1 + (int)(c & 1)); }
 		HIPCHK(hipEventRecord(e4[0], s1));
 		uint32_t* const pool = h->d_tok.p + (size_t)(c % h->k1_slots) * (size_t)h->slot_pages * K1_PAGE_WORDS;   // the chunk's slot of the token pool ring
 		launch_huff_tokens(h->d_comp.p, h->d_kdesc.p + c0, cn, h->d_status.p + c0, pool, (uint32_t)h->slot_pages, h->d_pool_ctr.p + c, h->d_tok_first.p + c0, h->d_tok_cnt.p + c0, h->d_work.p + c,
-		                   h->d_order.p + c0, h->p1_wgs, s1);
+		                   h->d_order.p + c0, h->p1_wgs, h->osw.p1_park, s1);
 		HIPCHK(hipEventRecord(e4[1], s1));
 	};
 	auto launch_p2 = [&](int64_t c) {
@@ -55,7 +54,7 @@ void enqueue_k1_tile(ngsqc_handle* h, int t)
 		if (h->verify_crc)   // htslib checks every member's CRC32 (bgzf.c); a mismatch fails the read
 		{
 			if (crc_stream != h->s_p2) HIPCHK(hipStreamWaitEvent(crc_stream, e4[3], 0));
-			launch_crc32(h->d_kdesc.p + c0, cn, out_base, h->d_crc.p + c0, h->d_status.p + c0, crc_stream);
+			launch_crc32(h->d_kdesc.p + c0, cn, out_base, h->d_crc.p + c0, h->d_status.p + c0, h->sw.crc_chains, crc_stream);
 		}
 	};
 	for (int64_t c = cA; c < cB; ++c) { launch_p1(c); launch_p2(c); }
@@ -106,7 +105,7 @@ const int64_t* ensure_recoff(ngsqc_handle* h)
 // record have been copied right in front of them). Tile-local coordinates: byte 0 = first carried byte.
 void index_tile(ngsqc_handle* h, int t)
 {
-	const bool dbg = getenv("NGSQC_DEBUG") != nullptr;
+	const bool dbg = h->sw.debug;
 	const int nt = (int)h->tiles.size();
 	const bool last = t == nt - 1;
 	const int64_t first = h->tiles[(size_t)t].first, nm = h->tiles[(size_t)t].second;
@@ -126,8 +125,8 @@ void index_tile(ngsqc_handle* h, int t)
 	if (t == 0)
 	{
 		h->long_reads = false;
-		const char* elr = getenv("NGSQC_LONG_READ_MODE");   // 0 / 1: never / always (tests); unset: by the first record
-		if (elr) h->long_reads = atoi(elr) != 0 && !anchor_by_guess;
+		const int elr = h->sw.long_read_mode;   // 0 / 1: never / always (tests); unset: by the first record
+		if (elr != SW_UNSET) h->long_reads = elr != 0 && !anchor_by_guess;
 		else if (!anchor_by_guess && exp0 >= 0 && exp0 + 4 <= total)
 		{
 			// (a sample, not one record: the mean block_size of up to eight records along the chain - an ONT file may well begin with a short read)
@@ -143,8 +142,8 @@ void index_tile(ngsqc_handle* h, int t)
 		}
 		h->lr_failures = 0;
 	}
-	int ksh = 0; if (const char* e = getenv("NGSQC_WALKERS")) { const int k = atoi(e); ksh = k >= 8 ? 3 : k >= 4 ? 2 : k >= 2 ? 1 : 0; }
-	if (h->long_reads) { ksh = K2_MIN_KSH; if (const char* e = getenv("NGSQC_GROUP_SHIFT")) ksh = -std::min(8, std::max(0, atoi(e))); }
+	int ksh = h->sw.walker_shift;
+	if (h->long_reads) ksh = h->sw.group_shift == SW_UNSET ? K2_MIN_KSH : -h->sw.group_shift;
 	if (anchor_by_guess || (h->k2_plain && !h->long_reads)) ksh = 0;
 	const int64_t ne0 = nm + 1;
 	int64_t ne = ksh >= 0 ? (nm << ksh) + 1 : ((nm + (1ll << -ksh) - 1) >> -ksh) + 1;
@@ -167,7 +166,7 @@ void index_tile(ngsqc_handle* h, int t)
 	HIPCHK(hipMemsetAsync(h->d_bad.p, 0, 2 * sizeof(uint32_t), h->stream)); HIPCHK(hipMemsetAsync(h->d_bad.p + 2, 0xff, sizeof(long long), h->stream));
 	h->fused_tile = -1;
 	// the job's first scan consumer rides K2's walk when the file has looked like an htslib file so far (one read of every record's first line instead of two)
-	const bool try_fuse = h->fuse && (h->fuse_ok || h->long_reads) && !anchor_by_guess && (prefix == 0 || h->long_reads) && !getenv("NGSQC_NO_FUSED_SCAN");   // (long reads: nearly every tile starts inside a carried record)
+	const bool try_fuse = h->fuse && (h->fuse_ok || h->long_reads) && !anchor_by_guess && (prefix == 0 || h->long_reads) && !h->sw.no_fused_scan;   // (long reads: nearly every tile starts inside a carried record)
 	const int64_t fuse_limit = h->shard_own_members >= 0 ? prefix + (h->shard_limit - u_lo) : INT64_MAX;   // a shard only scans the records that start in front of its limit
 	if (try_fuse)
 	{
@@ -187,7 +186,7 @@ void index_tile(ngsqc_handle* h, int t)
 	HIPCHK(hipStreamSynchronize(h->stream));
 	if (try_fuse) sm[2] = h->p_rb.p[A_LONG_COUNT];
 	const uint32_t n_corrupt = ((const uint32_t*)sm)[0], n_viol = ((const uint32_t*)sm)[1];
-	const bool aligned = !anchor_by_guess && n_viol == 0 && !getenv("NGSQC_K2_GENERAL");
+	const bool aligned = !anchor_by_guess && n_viol == 0 && !h->sw.k2_general;
 	if (try_fuse)
 	{
 		const bool lists_fit = sm[2] <= (unsigned long long)h->d_long.n && h->p_rb.p[ngsqc_handle::RB_BQ] <= h->fuse->fused_bq_cap();
@@ -349,7 +348,7 @@ void sync_all(ngsqc_handle* h)
 void stream_tiles(ngsqc_handle* h, const std::function<bool(const TileCtx&)>& f)
 {
 	plan_layout(h);
-	dbg_stamp("tile stream: layout ready");
+	dbg_stamp(h->sw.debug, "tile stream: layout ready");
 	const int nt = (int)h->tiles.size();
 	if (nt == 0) { h->decoded = true; h->n_rec = 0; return; }
 	if (nt == 1 && h->decoded && h->cur_tile == 0)
@@ -360,8 +359,8 @@ void stream_tiles(ngsqc_handle* h, const std::function<bool(const TileCtx&)>& f)
 	}
 	reset_decode_timings(h);
 	h->decoded = false; h->cur_tile = -1; h->k1_enq = 0; h->k2_plain = false;
-	const bool dbg = getenv("NGSQC_DEBUG") != nullptr;
-	const char* pe = getenv("NGSQC_PIPELINE"); const bool pipelined = !pe || atoi(pe) != 0;   // 0: K1 of a tile starts only when the previous tile is consumed (stage attribution)
+	const bool dbg = h->sw.debug;
+	const bool pipelined = h->sw.pipeline;   // 0: K1 of a tile starts only when the previous tile is consumed (stage attribution)
 	HIPCHK(hipMemsetAsync(h->d_work.p, 0, (size_t)h->nch * sizeof(unsigned long long), h->stream));
 	HIPCHK(hipMemsetAsync(h->d_pool_ctr.p, 0, (size_t)h->nch * sizeof(uint32_t), h->stream));
 	HIPCHK(hipStreamSynchronize(h->stream));

@@ -2,12 +2,7 @@
 // cache by read name, alignment_pass, BamWriter::writeAlignment) runs as one pass over the BAM on the GPU, and the BGZF writer deflates on the GPU as well
 // (ngsqc_filter_pairs: csrc/pairs.hip, csrc/deflate.hip).
 #include "Statistics.hpp"
-#include <chrono>
 using namespace ngsbits;
-
-static double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-static const double g_t0 = now_s();
-static void stamp(const char* what) { if (getenv("NGSQC_TIMING")) fprintf(stderr, "[ngsqc] +%.3f s %s\n", now_s() - g_t0, what); }
 
 static bool ends_with(const std::string& s, const std::string& e) { return s.size() >= e.size() && s.compare(s.size() - e.size(), e.size(), e) == 0; }
 

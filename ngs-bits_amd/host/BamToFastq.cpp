@@ -2,13 +2,8 @@
 // mate cache by read name, -fix, -remove_duplicates, alignmentToFastq) runs as one pass over the BAM on the GPU, and both FASTQ.GZ files are deflated on the
 // GPU as well (ngsqc_bam_to_fastq: csrc/fastq.hip, csrc/join.h, csrc/deflate.hip). The files are BGZF (valid gzip); their decompressed text is the reference's.
 #include "Statistics.hpp"
-#include <chrono>
 #include <regex>
 using namespace ngsbits;
-
-static double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-static const double g_t0 = now_s();
-static void stamp(const char* what) { if (getenv("NGSQC_TIMING")) fprintf(stderr, "[ngsqc] +%.3f s %s\n", now_s() - g_t0, what); }
 
 // Helper::toInt: the whole (trimmed) text is a decimal int
 static bool to_int(const std::string& t, int& v)

@@ -14,9 +14,6 @@ const char* const NO_REF = "<none>";
 BamReader::BamReader(const std::string& bam_file, const std::string& ref, bool allow_shards) : bam_file_(bam_file) { init(ref, allow_shards, nullptr, 0); }
 BamReader::BamReader(const std::string& bam_file, const std::string& ref, bool allow_shards, const BedFile& regions) : bam_file_(bam_file) { init(ref, allow_shards, &regions, 0); }
 BamReader::BamReader(const std::string& bam_file, const std::string& ref, Head head) : bam_file_(bam_file) { init(ref, false, nullptr, head.n_members); }
-static double now_s() { struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec; }
-static const double g_t0 = now_s();
-static void stamp(const char* what) { if (getenv("NGSQC_TIMING")) fprintf(stderr, "[ngsqc] +%.3f s %s\n", now_s() - g_t0, what); }
 
 void BamReader::requireTags(bool needed) { ngsqc_set_cram_skip(NGSQC_CRAM_SKIP_NAMES | (needed ? 0 : NGSQC_CRAM_SKIP_TAGS)); }
 static const bool g_cram_skip_default = (BamReader::requireTags(false), true);   // (tools: names never, tags only where a function says so)

@@ -22,6 +22,10 @@ std::string resourceDir()
 	return d + "/../resources";
 }
 
+double now_s() { struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec; }
+static const double g_t0 = now_s();
+void stamp(const char* what) { if (getenv("NGSQC_TIMING")) fprintf(stderr, "[ngsqc] +%.3f s %s\n", now_s() - g_t0, what); }
+
 const std::map<std::string, OntologyTerm>& qcmlTerms()
 {
 	static std::map<std::string, OntologyTerm> terms;

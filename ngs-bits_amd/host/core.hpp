@@ -356,6 +356,8 @@ struct QCValue
 };
 
 std::string resourceDir();   // ngs-bits_amd/resources (next to the tool binaries' parent)
+double now_s();                 // monotonic clock, seconds
+void stamp(const char* what);   // NGSQC_TIMING: seconds since the process's static initialisers, and what has just happened
 
 class QCCollection
 {

@@ -1,6 +1,7 @@
 """GPU parity on synthetic BAMs (sizes the oracle finishes in seconds): short-read WGS shape, unaligned BGZF members
 (records straddling members), ONT-like long reads with CG-tag CIGARs, coverage tools with min_baseq."""
 import os
+import re
 
 import numpy as np
 import pytest
@@ -332,7 +333,7 @@ def test_first_job_races_the_background_copy(tmp_path, monkeypatch):
 
 
 @pytest.mark.parametrize("tile_members", ["64", "200"])
-def test_streamed_image_equals_resident(tmp_path, monkeypatch, tile_members):
+def test_streamed_image_equals_resident(tmp_path, monkeypatch, capfd, tile_members):
     """Round 4: ngsqc_open(path) of a large file keeps no resident compressed image - every job copies the file through a ring of K1-chunk slots (a slot is refilled when
     phase 2 of the chunk that used it is done). Forced here on a small file with tiny chunks (tens of chunks through four slots, slowed-down copies): same records, counters
     and depth as the resident handle, for a second job on the same handle (the file crosses PCIe again), for the BAI pass, and with the second-chance path in the stream."""
@@ -341,7 +342,7 @@ def test_streamed_image_equals_resident(tmp_path, monkeypatch, tile_members):
     ob = O.Bam(path)
 
     def run(env, jobs=1):
-        for k in ("NGSQC_STREAM_IMAGE", "NGSQC_TILE_MEMBERS", "NGSQC_H2D_PIECE_MB", "NGSQC_H2D_DELAY_US", "NGSQC_TOKEN_POOL_FACTOR", "NGSQC_COMP_SLOTS"):
+        for k in ("NGSQC_STREAM_IMAGE", "NGSQC_TILE_MEMBERS", "NGSQC_H2D_PIECE_MB", "NGSQC_H2D_DELAY_US", "NGSQC_TOKEN_POOL_FACTOR", "NGSQC_COMP_SLOTS", "NGSQC_DEBUG"):
             monkeypatch.delenv(k, raising=False)
         for k, v in env.items():
             monkeypatch.setenv(k, v)
@@ -363,12 +364,14 @@ def test_streamed_image_equals_resident(tmp_path, monkeypatch, tile_members):
         for a, b in zip(got, ref):
             assert np.array_equal(a, b)
     # two slots only, and a token pool that runs dry in every chunk: the second chance reads its members' bytes from the file, not from the ring
-    res, t, _ = run({"NGSQC_STREAM_IMAGE": "1", "NGSQC_TILE_MEMBERS": tile_members, "NGSQC_COMP_SLOTS": "2", "NGSQC_TOKEN_POOL_FACTOR": "0.01"})
+    capfd.readouterr()
+    res, t, _ = run({"NGSQC_STREAM_IMAGE": "1", "NGSQC_TILE_MEMBERS": tile_members, "NGSQC_COMP_SLOTS": "2", "NGSQC_TOKEN_POOL_FACTOR": "0.01", "NGSQC_DEBUG": "1"})
+    assert re.search(r"\[ngsqc\] layout: \d+ tiles, \d+ chunks, 2 image slots,", capfd.readouterr().err)   # (the ring really has two slots)
     assert t["members_second_chance"] > 0
     for a, b in zip(res[0], ref):
         assert np.array_equal(a, b)
     # the index pass is one more trip of the file through the ring
-    monkeypatch.setenv("NGSQC_STREAM_IMAGE", "1"); monkeypatch.setenv("NGSQC_TILE_MEMBERS", tile_members); monkeypatch.delenv("NGSQC_TOKEN_POOL_FACTOR", raising=False)
+    monkeypatch.setenv("NGSQC_STREAM_IMAGE", "1"); monkeypatch.setenv("NGSQC_TILE_MEMBERS", tile_members); monkeypatch.delenv("NGSQC_TOKEN_POOL_FACTOR", raising=False); monkeypatch.delenv("NGSQC_DEBUG", raising=False)
     h = ngsqc.Handle(path=path)
     h.write_bai(str(tmp_path / "s.bai")); h.close()
     monkeypatch.setenv("NGSQC_STREAM_IMAGE", "0")
