@@ -307,6 +307,25 @@ int ngsqc_bgzf_compress(const void* in, size_t n, int device, void* out, size_t 
  * (byte-identical to it). Deterministic at every level. NGSQC_E_ARG for a level outside 0..9. */
 int ngsqc_bgzf_compress_level(const void* in, size_t n, int device, int level, void* out, size_t cap, size_t* out_n);
 
+/* ---- BamDownsample (src/BamDownsample/main.cpp:31-101) over the same join and writer. Records with flag 0x100 or 0x800 are skipped (:58). A record without
+ * flag 0x1 is a single-end record (:60-69): it draws the next random number and, when kept, is written at once. A record with flag 0x1 opens an entry for its
+ * exact read name or closes the open one (:70-91; names that occur 3, 4, 5 times pair as (1,2), (3,4), ...; no filter on mapped, MAPQ or mate flags); the
+ * closing record draws the next random number and, when kept, the opener and then the closer are written. Entries still open at the end are pe_unmatched (:100).
+ * The k-th deciding record in file order uses the k-th value of glibc's rand() behind srand(seed) (:36; seed 0 is seed 1 in glibc) as
+ * Helper::randomNumber(0, 100) = 0 + (double)rand() / RAND_MAX * 100, and is kept when that is < percentage (:63, :80). The output is written as
+ * ngsqc_filter_pairs writes it (header bytes, records byte for byte, CG-tag records as bam_write1 writes them, 0xff00-byte members, the EOF member).
+ * A percentage outside (0, 100) is NGSQC_E_ARG (:38), as is a handle on a shard, a range, regions or the first records. want_names != 0: *kept_names receives
+ * the kept deciding records in stream order as "SE\tname\n" / "PE\tname\n" lines (NUL-terminated, malloc'ed: the caller frees it; what -test prints, :67, :85);
+ * without want_names kept_names may be NULL, and *kept_names is set to NULL when it is not. */
+typedef struct { double percentage; uint32_t seed; int32_t want_names; } ngsqc_downsample_params;
+typedef struct { int64_t se, se_written, pe, pe_written, pe_unmatched; } ngsqc_downsample_counts;
+int ngsqc_downsample(ngsqc_handle* h, const ngsqc_downsample_params* p, const char* out_bam_path, ngsqc_downsample_counts* c, char** kept_names);
+/* The decision stream of that writer on its own (its generator on a range of ordinals; like ngsqc_bgzf_compress for the encoder): out[i] = 1 when the deciding
+ * record with ordinal first + i is kept, else 0. One device lane walks NGSQC_DOWNSAMPLE_CHUNK consecutive values from a start state that the host reaches by
+ * jumping, so the host work does not grow with first. NGSQC_E_ARG for a percentage outside (0, 100), first < 0 or n < 0. */
+#define NGSQC_DOWNSAMPLE_CHUNK 3968
+int ngsqc_downsample_keep(uint32_t seed, double percentage, int64_t first, int64_t n, int device, uint8_t* out);
+
 /* ---- BamToFastq (src/BamToFastq/main.cpp:77-214): the records of the handle in file order, secondary and supplementary records skipped; with remove_duplicates
  * the duplicates skipped and counted; with fix a record whose (name, read 1) pair came earlier in the file dropped and counted (the set of seen pairs lives in
  * device memory for the whole run). Paired-end mode (out2 not NULL and not ""): unpaired records are skipped and counted, the others are joined by read name

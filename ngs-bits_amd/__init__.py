@@ -9,5 +9,6 @@ from .capi import (  # noqa: F401
     MODE_ROI, MODE_NOROI, MODE_WGS, NCOUNTERS, COUNTER_NAMES, ShardSummary, ShardFix, SUMMARY_FIELDS, plan_shard_fix, bai_range, bai_ranges, set_reference, set_cram_skip, set_cram_skip_thread, CRAM_SKIP_NAMES, CRAM_SKIP_TAGS, cram_to_bam, bai_assemble, bgzf_scan, Comm, device_count,
     IndelWindow, VariantParams, ALLELE_NONE, ALLELE_INS, ALLELE_DEL, INDEL_COUNTER_NAMES,
     PairFilter, bgzf_compress, FastqParams, FastqCounts, FASTQ_COUNT_NAMES,
+    DownsampleParams, DownsampleCounts, DOWNSAMPLE_COUNT_NAMES, DOWNSAMPLE_CHUNK, downsample_keep,
 )
 from .dist import allreduce_counters, combine_counters_local, shard_blocks, scan_mapping_sharded, scan_mapping_sharded_local, scan_depth_sharded_local  # noqa: F401,E402

@@ -93,6 +93,18 @@ class FastqCounts(C.Structure):
     _fields_ = [(n, C.c_int64) for n in FASTQ_COUNT_NAMES]
 
 
+class DownsampleParams(C.Structure):
+    _fields_ = [("percentage", C.c_double), ("seed", C.c_uint32), ("want_names", C.c_int32)]
+
+
+DOWNSAMPLE_COUNT_NAMES = ("se", "se_written", "pe", "pe_written", "pe_unmatched")
+DOWNSAMPLE_CHUNK = 3968   # NGSQC_DOWNSAMPLE_CHUNK: the ordinals of the decision stream one device lane walks
+
+
+class DownsampleCounts(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in DOWNSAMPLE_COUNT_NAMES]
+
+
 class JobResult(C.Structure):
     _fields_ = [("counters", C.c_void_p), ("gc_reads", C.c_void_p), ("site_counts", C.c_void_p), ("read_stats", C.c_void_p)]
 
@@ -171,6 +183,8 @@ def lib():
         L.ngsqc_bgzf_compress.restype = i32; L.ngsqc_bgzf_compress.argtypes = [vp, C.c_size_t, i32, vp, C.c_size_t, C.POINTER(C.c_size_t)]
         L.ngsqc_bgzf_compress_level.restype = i32; L.ngsqc_bgzf_compress_level.argtypes = [vp, C.c_size_t, i32, i32, vp, C.c_size_t, C.POINTER(C.c_size_t)]
         L.ngsqc_bam_to_fastq.restype = i32; L.ngsqc_bam_to_fastq.argtypes = [vp, C.POINTER(FastqParams), cp, cp, C.POINTER(FastqCounts)]
+        L.ngsqc_downsample.restype = i32; L.ngsqc_downsample.argtypes = [vp, C.POINTER(DownsampleParams), cp, C.POINTER(DownsampleCounts), C.POINTER(vp)]
+        L.ngsqc_downsample_keep.restype = i32; L.ngsqc_downsample_keep.argtypes = [C.c_uint32, C.c_double, i64, i64, i32, vp]
         L.ngsqc_scan_reads.restype = i32; L.ngsqc_scan_reads.argtypes = [vp, C.c_int32, C.POINTER(ReadStats)]
         L.ngsqc_read_length_hist.restype = i32; L.ngsqc_read_length_hist.argtypes = [vp, vp, i64]
         L.ngsqc_read_cycle_stats.restype = i32; L.ngsqc_read_cycle_stats.argtypes = [vp, vp, i64]
@@ -217,6 +231,16 @@ def bgzf_compress(data, device=0, level=None):
     return bytes(out[:got.value])
 
 
+def downsample_keep(seed, percentage, first, n, device=0):
+    """The decisions of BamDownsample's random stream on their own (include/ngsqc.h ngsqc_downsample_keep): uint8[n], 1 where the deciding record with ordinal
+    first + i is kept at that percentage behind srand(seed)."""
+    out = np.zeros(max(int(n), 1), dtype=np.uint8)
+    rc = lib().ngsqc_downsample_keep(int(seed) & 0xFFFFFFFF, float(percentage), int(first), int(n), int(device), out.ctypes.data)
+    if rc:
+        raise NgsqcError(rc, "downsample_keep failed")
+    return out[:int(n)]
+
+
 def device_count():
     """HIP devices the library's own runtime sees (include/ngsqc.h ngsqc_device_count) - not torch's: a second HIP / HSA runtime in the process is what a test that
     only wants a number must not load."""
@@ -233,7 +257,7 @@ EXPORTS = [
     "ngsqc_run_job", "ngsqc_depth_select", "ngsqc_depth_reduce", "ngsqc_region_read_counts", "ngsqc_upload_wait", "ngsqc_run_job_partial", "ngsqc_bai_range", "ngsqc_open_range", "ngsqc_header_text", "ngsqc_open_regions", "ngsqc_open_head",
     "ngsqc_write_bai", "ngsqc_bai_assemble", "ngsqc_bgzf_scan", "ngsqc_write_csi", "ngsqc_csi_assemble", "ngsqc_bai_ranges",
     "ngsqc_set_reference", "ngsqc_set_cram_skip", "ngsqc_set_cram_skip_thread", "ngsqc_cram_to_bam", "ngsqc_indel_windows", "ngsqc_variant_details",
-    "ngsqc_filter_pairs", "ngsqc_bgzf_compress", "ngsqc_bgzf_compress_level", "ngsqc_bam_to_fastq",
+    "ngsqc_filter_pairs", "ngsqc_bgzf_compress", "ngsqc_bgzf_compress_level", "ngsqc_bam_to_fastq", "ngsqc_downsample", "ngsqc_downsample_keep",
 ]
 
 
@@ -602,6 +626,20 @@ class Handle:
         cnt = FastqCounts()
         self._chk(lib().ngsqc_bam_to_fastq(self.h, C.byref(p), os.fsencode(out1), os.fsencode(out2) if out2 else None, C.byref(cnt)))
         return {n: int(getattr(cnt, n)) for n in FASTQ_COUNT_NAMES}
+
+    def downsample(self, out_path, percentage, seed=1, want_names=False):
+        """BamDownsample (src/BamDownsample/main.cpp) of the whole file into the BAM out_path (include/ngsqc.h ngsqc_downsample). Returns the counts as a dict
+        (DOWNSAMPLE_COUNT_NAMES); with want_names (counts, kept names): the "SE\tname\n" / "PE\tname\n" lines of the kept deciding records as bytes."""
+        p = DownsampleParams(float(percentage), int(seed) & 0xFFFFFFFF, int(bool(want_names)))
+        cnt, names = DownsampleCounts(), C.c_void_p()
+        self._chk(lib().ngsqc_downsample(self.h, C.byref(p), os.fsencode(out_path), C.byref(cnt), C.byref(names)))
+        counts = {n: int(getattr(cnt, n)) for n in DOWNSAMPLE_COUNT_NAMES}
+        if not want_names:
+            return counts
+        try:
+            return counts, C.string_at(names.value)
+        finally:
+            libc = C.CDLL(None); libc.free.argtypes = [C.c_void_p]; libc.free(names)
 
     # ---- one BAM sharded over several handles (include/ngsqc.h, "sharded" section) ----
     def scan_mapping_partial(self, mode, **kw):

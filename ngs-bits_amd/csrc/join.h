@@ -1,5 +1,5 @@
 // The mate join by read name and the windowed BGZF writer, shared by the tools that pair records and write compressed output (BamFilter: pairs.hip,
-// BamToFastq: fastq.hip). One pass over the tiles; per tile (NameJoin):
+// BamToFastq: fastq.hip, BamDownsample: downsample.hip). One pass over the tiles; per tile (NameJoin):
 //   1. the tool's keys kernel gives every tile record a 64-bit name hash (KEY_NONE: the record takes no part), its source pointer and a 32-bit info word whose
 //      bit 31 says the record is kept ("passes"); val[e] = e for every entry.
 //   2. sort: the open entries carried over from earlier tiles ("held", in (hash, ordinal) order) followed by the tile's records, radix-sorted by hash (rocPRIM,
