@@ -13,23 +13,10 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ngsqc = __import__("importlib").import_module("ngs-bits_amd")
 
+from readprofile import sequential   # (the sequential model of the two carries: shared with the designed GPU tests)
+
 MODEL = r'''
 import numpy as np
-
-def sequential(recs):
-    """recs: int array [n, 4] = (length, counted, passing, paired). Reference order semantics."""
-    runmax, paired_seen, trimmed, no_overlap, n_counted = 0, False, 0, 0, 0
-    for ln, counted, passing, paired in recs:
-        if not counted:
-            continue
-        n_counted += 1
-        runmax = max(runmax, ln)
-        trimmed += runmax - ln
-        if paired:
-            paired_seen = True
-        if passing and paired_seen:
-            no_overlap += ln
-    return dict(n=n_counted, trimmed=trimmed, no_overlap=no_overlap, gmax=runmax, paired=int(paired_seen))
 
 class ShardModel:
     """What a shard handle does, on a slice of the record list (mirrors scan_mapping_partial / scan_mapping_finish)."""
@@ -109,10 +96,12 @@ def test_chain_mismatch_between_shards_is_an_error():
     assert "record chain" in str(e.value)
 
 
-_WORKER = MODEL + r'''
+_WORKER = r'''
 import importlib, os, sys
+sys.path.insert(0, sys.argv[1]); sys.path.insert(0, sys.argv[1] + "/tests")
+from readprofile import sequential
+''' + MODEL + r'''
 import torch.distributed as dist
-sys.path.insert(0, sys.argv[1])
 ngsqc = importlib.import_module("ngs-bits_amd")
 rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
 dist.init_process_group(backend="gloo", rank=rank, world_size=world)
