@@ -326,6 +326,23 @@ int ngsqc_downsample(ngsqc_handle* h, const ngsqc_downsample_params* p, const ch
 #define NGSQC_DOWNSAMPLE_CHUNK 3968
 int ngsqc_downsample_keep(uint32_t seed, double percentage, int64_t first, int64_t n, int device, uint8_t* out);
 
+/* ---- BamExtract (src/BamExtract/main.cpp:27-83) over the same writer, without the join. EVERY record of the file is a candidate (:64-76): secondary,
+ * supplementary and unmapped records are looked up and written like any other. A record whose name is one of the listed names goes to out_bam_path (:66-70);
+ * with out2_bam_path (not NULL and not "") every other record goes there (:71-75); without it the others are neither written nor counted. Each output holds
+ * its records in file order. A record's name is what BamAlignment::name() returns (src/cppNGS/BamReader.h:69-72, bam_get_qname read as a C string): the bytes
+ * in front of the first NUL of its l_read_name bytes. The listed names are the n_names byte strings laid end to end in names, name_len[i] bytes each, with
+ * no separators; duplicates are taken once. A listed name that no record can carry (no bytes, more than 254 bytes, a NUL byte inside) matches nothing and still
+ * counts as listed. counts->names: the distinct listed names (the reference's ids.count(), :45). The set of names lives in device memory for the call (a hash
+ * table of 16 bytes per slot, at least two slots per name, next to the names' bytes): NGSQC_E_DEVICE "BamExtract: the set of read names does not fit in device
+ * memory (N MiB needed, M MiB free)" when it does not fit. Both outputs are written as ngsqc_filter_pairs writes its output (header bytes, records byte for
+ * byte, CG-tag records as bam_write1 writes them, 0xff00-byte members, the EOF member). NGSQC_E_ARG for a null pointer, a negative count or length, and for a
+ * handle on a shard, a range, regions or the first records. */
+typedef struct { int64_t out, out2, names; } ngsqc_extract_counts;
+int ngsqc_extract_reads(ngsqc_handle* h, const void* names, const int32_t* name_len, int64_t n_names, const char* out_bam_path, const char* out2_bam_path, ngsqc_extract_counts* counts);
+/* The lookup of that tool on its own (like ngsqc_downsample_keep for the decision stream): match_out[i] = 1 when the name of the i-th record of the file, in
+ * file order, is one of the listed names, else 0. No file is written. cap: the bytes match_out holds; NGSQC_E_ARG when the file has more records. */
+int ngsqc_match_names(ngsqc_handle* h, const void* names, const int32_t* name_len, int64_t n_names, uint8_t* match_out, int64_t cap);
+
 /* ---- BamToFastq (src/BamToFastq/main.cpp:77-214): the records of the handle in file order, secondary and supplementary records skipped; with remove_duplicates
  * the duplicates skipped and counted; with fix a record whose (name, read 1) pair came earlier in the file dropped and counted (the set of seen pairs lives in
  * device memory for the whole run). Paired-end mode (out2 not NULL and not ""): unpaired records are skipped and counted, the others are joined by read name

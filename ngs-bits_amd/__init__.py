@@ -10,5 +10,6 @@ from .capi import (  # noqa: F401
     IndelWindow, VariantParams, ALLELE_NONE, ALLELE_INS, ALLELE_DEL, INDEL_COUNTER_NAMES,
     PairFilter, bgzf_compress, FastqParams, FastqCounts, FASTQ_COUNT_NAMES,
     DownsampleParams, DownsampleCounts, DOWNSAMPLE_COUNT_NAMES, DOWNSAMPLE_CHUNK, downsample_keep,
+    ExtractCounts, EXTRACT_COUNT_NAMES,
 )
 from .dist import allreduce_counters, combine_counters_local, shard_blocks, scan_mapping_sharded, scan_mapping_sharded_local, scan_depth_sharded_local  # noqa: F401,E402

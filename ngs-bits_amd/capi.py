@@ -105,6 +105,13 @@ class DownsampleCounts(C.Structure):
     _fields_ = [(n, C.c_int64) for n in DOWNSAMPLE_COUNT_NAMES]
 
 
+EXTRACT_COUNT_NAMES = ("out", "out2", "names")
+
+
+class ExtractCounts(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in EXTRACT_COUNT_NAMES]
+
+
 class JobResult(C.Structure):
     _fields_ = [("counters", C.c_void_p), ("gc_reads", C.c_void_p), ("site_counts", C.c_void_p), ("read_stats", C.c_void_p)]
 
@@ -185,6 +192,8 @@ def lib():
         L.ngsqc_bam_to_fastq.restype = i32; L.ngsqc_bam_to_fastq.argtypes = [vp, C.POINTER(FastqParams), cp, cp, C.POINTER(FastqCounts)]
         L.ngsqc_downsample.restype = i32; L.ngsqc_downsample.argtypes = [vp, C.POINTER(DownsampleParams), cp, C.POINTER(DownsampleCounts), C.POINTER(vp)]
         L.ngsqc_downsample_keep.restype = i32; L.ngsqc_downsample_keep.argtypes = [C.c_uint32, C.c_double, i64, i64, i32, vp]
+        L.ngsqc_extract_reads.restype = i32; L.ngsqc_extract_reads.argtypes = [vp, vp, vp, i64, cp, cp, C.POINTER(ExtractCounts)]
+        L.ngsqc_match_names.restype = i32; L.ngsqc_match_names.argtypes = [vp, vp, vp, i64, vp, i64]
         L.ngsqc_scan_reads.restype = i32; L.ngsqc_scan_reads.argtypes = [vp, C.c_int32, C.POINTER(ReadStats)]
         L.ngsqc_read_length_hist.restype = i32; L.ngsqc_read_length_hist.argtypes = [vp, vp, i64]
         L.ngsqc_read_cycle_stats.restype = i32; L.ngsqc_read_cycle_stats.argtypes = [vp, vp, i64]
@@ -258,6 +267,7 @@ EXPORTS = [
     "ngsqc_write_bai", "ngsqc_bai_assemble", "ngsqc_bgzf_scan", "ngsqc_write_csi", "ngsqc_csi_assemble", "ngsqc_bai_ranges",
     "ngsqc_set_reference", "ngsqc_set_cram_skip", "ngsqc_set_cram_skip_thread", "ngsqc_cram_to_bam", "ngsqc_indel_windows", "ngsqc_variant_details",
     "ngsqc_filter_pairs", "ngsqc_bgzf_compress", "ngsqc_bgzf_compress_level", "ngsqc_bam_to_fastq", "ngsqc_downsample", "ngsqc_downsample_keep",
+    "ngsqc_extract_reads", "ngsqc_match_names",
 ]
 
 
@@ -394,6 +404,13 @@ def _regions_array(regions):
 
 def _bytes(x):
     return x.encode("ascii") if isinstance(x, str) else bytes(x)
+
+
+def _names_buffer(names):
+    """names: an iterable of bytes. Returns (the names laid end to end, int32 lengths, their number) as ngsqc_extract_reads / ngsqc_match_names take them."""
+    names = [bytes(n) for n in names]
+    lens = np.array([len(n) for n in names], dtype=np.int32) if names else np.zeros(1, np.int32)
+    return b"".join(names), lens, len(names)
 
 
 def _windows_array(windows):
@@ -640,6 +657,24 @@ class Handle:
             return counts, C.string_at(names.value)
         finally:
             libc = C.CDLL(None); libc.free.argtypes = [C.c_void_p]; libc.free(names)
+
+    def extract(self, out, names, out2=None):
+        """BamExtract (src/BamExtract/main.cpp) of the whole file (include/ngsqc.h ngsqc_extract_reads): the records whose name is one of names (an iterable of
+        bytes) into the BAM out, with out2 every other record into the BAM out2. Returns the counts as a dict (EXTRACT_COUNT_NAMES: records written to out and
+        to out2, distinct names listed)."""
+        buf, lens, n = _names_buffer(names)
+        cnt = ExtractCounts()
+        self._chk(lib().ngsqc_extract_reads(self.h, buf, lens.ctypes.data, n, os.fsencode(out), os.fsencode(out2) if out2 else None, C.byref(cnt)))
+        return {k: int(getattr(cnt, k)) for k in EXTRACT_COUNT_NAMES}
+
+    def match_names(self, names):
+        """The lookup of BamExtract on its own (include/ngsqc.h ngsqc_match_names): uint8 per record of the file in file order, 1 where the record's name is one of
+        names (an iterable of bytes)."""
+        buf, lens, n = _names_buffer(names)
+        cap = self.n_records
+        out = np.zeros(max(cap, 1), dtype=np.uint8)
+        self._chk(lib().ngsqc_match_names(self.h, buf, lens.ctypes.data, n, out.ctypes.data, cap))
+        return out[:cap]
 
     # ---- one BAM sharded over several handles (include/ngsqc.h, "sharded" section) ----
     def scan_mapping_partial(self, mode, **kw):
