@@ -343,6 +343,34 @@ int ngsqc_extract_reads(ngsqc_handle* h, const void* names, const int32_t* name_
  * file order, is one of the listed names, else 0. No file is written. cap: the bytes match_out holds; NGSQC_E_ARG when the file has more records. */
 int ngsqc_match_names(ngsqc_handle* h, const void* names, const int32_t* name_len, int64_t n_names, uint8_t* match_out, int64_t cap);
 
+/* ---- BamRemoveVariants (src/BamRemoveVariants/main.cpp:34-278) over the same join and writer: read pairs that carry a variant of a VCF are dropped, or with
+ * mask kept with the reference base put back. Records with flag 0x100 or 0x800 are counted as skipped and take no further part (:141-145); every other record
+ * takes part. A table line overlaps a record when tid matches and [beg, end] meets [pos + 1, pos + max(1, reference length)] (the reference length is 0 with flag
+ * 0x4 or without a CIGAR: bam_endpos; a record with tid < 0 or pos < 0 overlaps nothing). The overlapping lines are visited in table order:
+ *   SNV      the base at `start` by BamAlignment::extractBaseByCIGAR (src/cppNGS/BamReader.cpp:307-374); the record carries the line when that base is obs. An
+ *            index outside [0, l_seq), which the reference reads past the sequence, gives no base. A walk that ends in front of start: error POS_NOT_FOUND (:373).
+ *   OTHER    the record carries the line when extractIndelsByCIGAR(start, 50) (:376-439) is non-empty: an I / D operation at a genome position in [start - 50, start + 50].
+ *   INVALID  error INVALID_LINE (what Variant(const VcfLine&) throws, src/cppNGS/VariantList.cpp:59).
+ * Default mode: the visit ends at the first carried line, and the record passes when there is none. mask: a carried SNV sets the base to ref (setBases,
+ * BamReader.cpp:133-175, rewrites the whole sequence: a base other than A, C, G, T, N anywhere in the read is error BAD_BASE), later lines see the new base; the
+ * first carried OTHER line ends the visit and the record passes when keep_indels is set; without one it passes. modified: the sequence differs from the input's.
+ * An error ends the visit and the record does not pass. Pairing is ngsqc_filter_pairs' rule (the first record of a name opens, the next closes): a pair is written,
+ * opener then closer, at the closer's position when both pass; passed / dropped count closed pairs. A closer is only visited when its opener passed (:218, :251):
+ * its modified and its error do not count otherwise; an opener's always do. single_end: no join, a record that passes is written at its own position, passed /
+ * dropped count records, modified counts written records (:155-160). The first error in file order stops the run: NGSQC_E_FORMAT with the reference's message, and
+ * counts->err_record (ordinal in the file), err_code and err_variant (index into variants; for BAD_BASE the index of the base in the read) say where.
+ * variants: n lines in file order; the lines of one tid must be contiguous with non-decreasing beg (NGSQC_E_ARG otherwise); lines with tid < 0 or beyond the
+ * header are ignored. The table lives in device memory for the call next to the running maximum of end, by which a record finds its first candidate line. */
+enum { NGSQC_RMVAR_SNV = 0, NGSQC_RMVAR_OTHER = 1, NGSQC_RMVAR_INVALID = 2 };
+enum { NGSQC_RMERR_NONE = 0, NGSQC_RMERR_INVALID_LINE = 1, NGSQC_RMERR_POS_NOT_FOUND = 2, NGSQC_RMERR_BAD_BASE = 3 };
+typedef struct { int32_t tid, beg, end, start; uint8_t kind, ref, obs, pad; } ngsqc_rm_variant;   /* beg = POS, end = POS + len(REF) - 1, start: after normalize("-", true); ref / obs: the SNV's bases */
+typedef struct { int32_t mask, single_end, keep_indels; } ngsqc_rm_params;
+typedef struct { int64_t passed, dropped, modified, skipped; int64_t err_record; int32_t err_code, err_variant; } ngsqc_rm_counts;
+int ngsqc_remove_variants(ngsqc_handle* h, const ngsqc_rm_variant* variants, int64_t n, const ngsqc_rm_params* p, const char* out_bam_path, ngsqc_rm_counts* counts);
+/* The verdicts of that tool on their own (like ngsqc_match_names): out[i] for the i-th record of the file, the record's own visit whatever its mate's:
+ * bit 0 passes, bit 1 modified, bit 2 skipped (flag 0x900), bit 3 error. No file is written. cap: the bytes out holds; NGSQC_E_ARG when the file has more records. */
+int ngsqc_variant_verdicts(ngsqc_handle* h, const ngsqc_rm_variant* variants, int64_t n, const ngsqc_rm_params* p, uint8_t* out, int64_t cap);
+
 /* ---- BamToFastq (src/BamToFastq/main.cpp:77-214): the records of the handle in file order, secondary and supplementary records skipped; with remove_duplicates
  * the duplicates skipped and counted; with fix a record whose (name, read 1) pair came earlier in the file dropped and counted (the set of seen pairs lives in
  * device memory for the whole run). Paired-end mode (out2 not NULL and not ""): unpaired records are skipped and counted, the others are joined by read name

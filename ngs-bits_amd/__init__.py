@@ -11,5 +11,6 @@ from .capi import (  # noqa: F401
     PairFilter, bgzf_compress, FastqParams, FastqCounts, FASTQ_COUNT_NAMES,
     DownsampleParams, DownsampleCounts, DOWNSAMPLE_COUNT_NAMES, DOWNSAMPLE_CHUNK, downsample_keep,
     ExtractCounts, EXTRACT_COUNT_NAMES,
+    RmVariant, RmParams, RmCounts, RM_COUNT_NAMES, RMVAR_SNV, RMVAR_OTHER, RMVAR_INVALID, RMERR_NONE, RMERR_INVALID_LINE, RMERR_POS_NOT_FOUND, RMERR_BAD_BASE,
 )
 from .dist import allreduce_counters, combine_counters_local, shard_blocks, scan_mapping_sharded, scan_mapping_sharded_local, scan_depth_sharded_local  # noqa: F401,E402

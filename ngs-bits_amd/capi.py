@@ -112,6 +112,24 @@ class ExtractCounts(C.Structure):
     _fields_ = [(n, C.c_int64) for n in EXTRACT_COUNT_NAMES]
 
 
+RM_COUNT_NAMES = ("passed", "dropped", "modified", "skipped")
+RMVAR_SNV, RMVAR_OTHER, RMVAR_INVALID = 0, 1, 2
+RMERR_NONE, RMERR_INVALID_LINE, RMERR_POS_NOT_FOUND, RMERR_BAD_BASE = 0, 1, 2, 3
+
+
+class RmVariant(C.Structure):
+    """One line of the variant table of BamRemoveVariants (include/ngsqc.h ngsqc_rm_variant)"""
+    _fields_ = [("tid", C.c_int32), ("beg", C.c_int32), ("end", C.c_int32), ("start", C.c_int32), ("kind", C.c_uint8), ("ref", C.c_uint8), ("obs", C.c_uint8), ("pad", C.c_uint8)]
+
+
+class RmParams(C.Structure):
+    _fields_ = [("mask", C.c_int32), ("single_end", C.c_int32), ("keep_indels", C.c_int32)]
+
+
+class RmCounts(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in RM_COUNT_NAMES] + [("err_record", C.c_int64), ("err_code", C.c_int32), ("err_variant", C.c_int32)]
+
+
 class JobResult(C.Structure):
     _fields_ = [("counters", C.c_void_p), ("gc_reads", C.c_void_p), ("site_counts", C.c_void_p), ("read_stats", C.c_void_p)]
 
@@ -194,6 +212,8 @@ def lib():
         L.ngsqc_downsample_keep.restype = i32; L.ngsqc_downsample_keep.argtypes = [C.c_uint32, C.c_double, i64, i64, i32, vp]
         L.ngsqc_extract_reads.restype = i32; L.ngsqc_extract_reads.argtypes = [vp, vp, vp, i64, cp, cp, C.POINTER(ExtractCounts)]
         L.ngsqc_match_names.restype = i32; L.ngsqc_match_names.argtypes = [vp, vp, vp, i64, vp, i64]
+        L.ngsqc_remove_variants.restype = i32; L.ngsqc_remove_variants.argtypes = [vp, vp, i64, C.POINTER(RmParams), cp, C.POINTER(RmCounts)]
+        L.ngsqc_variant_verdicts.restype = i32; L.ngsqc_variant_verdicts.argtypes = [vp, vp, i64, C.POINTER(RmParams), vp, i64]
         L.ngsqc_scan_reads.restype = i32; L.ngsqc_scan_reads.argtypes = [vp, C.c_int32, C.POINTER(ReadStats)]
         L.ngsqc_read_length_hist.restype = i32; L.ngsqc_read_length_hist.argtypes = [vp, vp, i64]
         L.ngsqc_read_cycle_stats.restype = i32; L.ngsqc_read_cycle_stats.argtypes = [vp, vp, i64]
@@ -267,7 +287,7 @@ EXPORTS = [
     "ngsqc_write_bai", "ngsqc_bai_assemble", "ngsqc_bgzf_scan", "ngsqc_write_csi", "ngsqc_csi_assemble", "ngsqc_bai_ranges",
     "ngsqc_set_reference", "ngsqc_set_cram_skip", "ngsqc_set_cram_skip_thread", "ngsqc_cram_to_bam", "ngsqc_indel_windows", "ngsqc_variant_details",
     "ngsqc_filter_pairs", "ngsqc_bgzf_compress", "ngsqc_bgzf_compress_level", "ngsqc_bam_to_fastq", "ngsqc_downsample", "ngsqc_downsample_keep",
-    "ngsqc_extract_reads", "ngsqc_match_names",
+    "ngsqc_extract_reads", "ngsqc_match_names", "ngsqc_remove_variants", "ngsqc_variant_verdicts",
 ]
 
 
@@ -404,6 +424,20 @@ def _regions_array(regions):
 
 def _bytes(x):
     return x.encode("ascii") if isinstance(x, str) else bytes(x)
+
+
+def _variants_buffer(variants):
+    """variants: an iterable of RmVariant, or of (tid, beg, end, start, kind, ref, obs) with ref / obs as bytes of length 1 or integers. Returns (array, n)."""
+    rows = list(variants)
+    arr = (RmVariant * max(len(rows), 1))()
+    for i, v in enumerate(rows):
+        if isinstance(v, RmVariant):
+            arr[i] = v
+        else:
+            tid, beg, end, start, kind, ref, obs = v
+            arr[i] = RmVariant(tid, beg, end, start, kind, ref[0] if isinstance(ref, (bytes, bytearray)) and ref else int(ref or 0),
+                               obs[0] if isinstance(obs, (bytes, bytearray)) and obs else int(obs or 0), 0)
+    return arr, len(rows)
 
 
 def _names_buffer(names):
@@ -675,6 +709,30 @@ class Handle:
         out = np.zeros(max(cap, 1), dtype=np.uint8)
         self._chk(lib().ngsqc_match_names(self.h, buf, lens.ctypes.data, n, out.ctypes.data, cap))
         return out[:cap]
+
+    def remove_variants(self, out, variants, mask=False, single_end=False, keep_indels=False):
+        """BamRemoveVariants (src/BamRemoveVariants/main.cpp) of the whole file (include/ngsqc.h ngsqc_remove_variants): the read pairs (single_end: the reads)
+        that carry none of the variants into the BAM out; with mask the carried SNVs set back to the reference base instead. variants: the table lines in file
+        order (RmVariant, or tuples: _variants_buffer). Returns the counts as a dict (RM_COUNT_NAMES). An error of a record raises with the reference's message;
+        the exception's rm_error holds (ordinal of the record, error code, variant index)."""
+        arr, n = _variants_buffer(variants)
+        p, cnt = RmParams(int(mask), int(single_end), int(keep_indels)), RmCounts()
+        try:
+            self._chk(lib().ngsqc_remove_variants(self.h, arr, n, C.byref(p), os.fsencode(out), C.byref(cnt)))
+        except Exception as e:
+            e.rm_error = (int(cnt.err_record), int(cnt.err_code), int(cnt.err_variant))
+            raise
+        return {k: int(getattr(cnt, k)) for k in RM_COUNT_NAMES}
+
+    def variant_verdicts(self, variants, mask=False, single_end=False, keep_indels=False):
+        """The verdicts of BamRemoveVariants on their own (include/ngsqc.h ngsqc_variant_verdicts): bytes, one per record of the file in file order: bit 0 passes,
+        bit 1 modified, bit 2 skipped, bit 3 error - the record's own visit, whatever its mate's."""
+        arr, n = _variants_buffer(variants)
+        p = RmParams(int(mask), int(single_end), int(keep_indels))
+        cap = self.n_records
+        out = np.zeros(max(cap, 1), dtype=np.uint8)
+        self._chk(lib().ngsqc_variant_verdicts(self.h, arr, n, C.byref(p), out.ctypes.data, cap))
+        return out[:cap].tobytes()
 
     # ---- one BAM sharded over several handles (include/ngsqc.h, "sharded" section) ----
     def scan_mapping_partial(self, mode, **kw):

@@ -113,21 +113,6 @@ __global__ __launch_bounds__(256) void ex_gather_kernel(const uint8_t* __restric
 	}
 }
 
-// HIP-event intervals of NGSQC_TIMING, read once at the end of the call
-struct StageClock
-{
-	bool on; hipStream_t s; std::vector<hipEvent_t> ev;
-	StageClock(bool o, hipStream_t st) : on(o), s(st) {}
-	void mark() { if (!on) return; hipEvent_t e; HIPCHK(hipEventCreate(&e)); HIPCHK(hipEventRecord(e, s)); ev.push_back(e); }   // (called in pairs: begin, end)
-	double total()
-	{
-		double ms = 0;
-		for (size_t i = 0; i + 1 < ev.size(); i += 2) { float v = 0; if (hipEventSynchronize(ev[i + 1]) == hipSuccess && hipEventElapsedTime(&v, ev[i], ev[i + 1]) == hipSuccess) ms += v; }
-		return ms;
-	}
-	~StageClock() { for (hipEvent_t e : ev) (void)hipEventDestroy(e); }
-};
-
 // the set of the listed names on the device
 struct NameSet
 {

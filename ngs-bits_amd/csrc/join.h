@@ -256,6 +256,21 @@ struct NameJoin
 	void read_counts(unsigned long long* c, hipStream_t s) { HIPCHK(hipMemcpyAsync(c, counts.p, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s)); HIPCHK(hipStreamSynchronize(s)); }
 };
 
+// HIP-event intervals of NGSQC_TIMING, read once at the end of the call
+struct StageClock
+{
+	bool on; hipStream_t s; std::vector<hipEvent_t> ev;
+	StageClock(bool o, hipStream_t st) : on(o), s(st) {}
+	void mark() { if (!on) return; hipEvent_t e; HIPCHK(hipEventCreate(&e)); HIPCHK(hipEventRecord(e, s)); ev.push_back(e); }   // (called in pairs: begin, end)
+	double total()
+	{
+		double ms = 0;
+		for (size_t i = 0; i + 1 < ev.size(); i += 2) { float v = 0; if (hipEventSynchronize(ev[i + 1]) == hipSuccess && hipEventElapsedTime(&v, ev[i], ev[i + 1]) == hipSuccess) ms += v; }
+		return ms;
+	}
+	~StageClock() { for (hipEvent_t e : ev) (void)hipEventDestroy(e); }
+};
+
 // one output stream in windows of W bytes (NGSQC_WRITE_WINDOW_PIECES: pieces of 0xff00 bytes per window, a test hook; default about 1 GiB): its device and pinned
 // memory does not depend on the size of the file or of a tile
 inline int64_t write_window_bytes(int64_t pieces) { return pieces * BGZF_PIECE; }

@@ -1,6 +1,10 @@
 // The BAM record as the device kernels read it (scan.hip, indel.hip): the fixed fields, the effective CIGAR, the aux scan, a wave reduction.
 #pragma once
+#ifdef NGSQC_REC_ON_CPU   // tests/emul: the record view as plain C++
+#include <cstdint>
+#else
 #include "common.h"
+#endif
 
 namespace ngsqc {
 
@@ -87,11 +91,13 @@ __device__ static int aux_tagi(const RecView& r, uint8_t t0, uint8_t t1)
 	}
 }
 
+#ifndef NGSQC_REC_ON_CPU
 __device__ __forceinline__ long long wave_sum(long long v)
 {
 	for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
 	return v;
 }
+#endif
 
 // CG:B,I long CIGAR (htslib bam_tag2cigar): on a placed record (tid >= 0 and pos >= 0), behind a first operation kS with k == l_seq, the tag's array replaces the
 // CIGAR when it holds at least n_cigar operations (the oracle's parse_rec, oracle/bamio.hpp). rec_cg_tag looks the tag up (the caller has checked the first operation): the array, or null; rec_apply_cg does both for one record

@@ -3,6 +3,7 @@
 // the parity tests exercise host/core.cpp as well. Built as bin/libngsqc_hostapi.so; not part of the C ABI of include/ngsqc.h.
 #include "core.hpp"
 #include "Variant.hpp"
+#include "RmVariants.hpp"
 #include <cstring>
 using namespace ngsbits;
 
@@ -63,6 +64,24 @@ int ngsbits_variant_region(const char* fasta, const char* chr, int pos, const ch
 			*reg_first = reg.first; *reg_second = reg.second;
 		}
 		return 0;
+	}
+	catch (std::exception& e) { return fail(e, err, err_cap); }
+}
+
+// The variant table of BamRemoveVariants (host/RmVariants.hpp: loadRmVariants) for the references of a BAM in tid order. out: rows (tid or -1, beg, end, start, kind,
+// ref, obs), one per data line in file order. Returns the number of lines (also when it exceeds cap), -1 on an error (message in err).
+long long ngsbits_rm_variants(const char* vcf_path, const char* const* ref_names, int n_ref, int* out, long long cap, char* err, int err_cap)
+{
+	try
+	{
+		const RmVariantTable t = loadRmVariants(vcf_path, std::vector<std::string>(ref_names, ref_names + n_ref));
+		for (long long i = 0; i < (long long)t.lines.size() && i < cap; ++i)
+		{
+			const ngsqc_rm_variant& v = t.lines[(size_t)i];
+			int* o = out + 7 * i;
+			o[0] = v.tid; o[1] = v.beg; o[2] = v.end; o[3] = v.start; o[4] = v.kind; o[5] = v.ref; o[6] = v.obs;
+		}
+		return (long long)t.lines.size();
 	}
 	catch (std::exception& e) { return fail(e, err, err_cap); }
 }
