@@ -371,6 +371,31 @@ int ngsqc_remove_variants(ngsqc_handle* h, const ngsqc_rm_variant* variants, int
  * bit 0 passes, bit 1 modified, bit 2 skipped (flag 0x900), bit 3 error. No file is written. cap: the bytes out holds; NGSQC_E_ARG when the file has more records. */
 int ngsqc_variant_verdicts(ngsqc_handle* h, const ngsqc_rm_variant* variants, int64_t n, const ngsqc_rm_params* p, uint8_t* out, int64_t cap);
 
+/* ---- BamClipOverlap (src/BamClipOverlap/main.cpp:43-554, NGSHelper::softClipAlignment NGSHelper.cpp:670-810): the read pairs of the whole file whose two
+ * alignments overlap are soft-clipped so that every reference base is covered by one of them. A record that is unpaired, secondary, supplementary, unmapped,
+ * whose mate is unmapped or on another reference, or whose CIGAR holds only I / S (as htslib shows it: a CG tag's CIGAR in place) is written as it is at its own
+ * place. Every other record enters the name map: the 1st and 2nd record of a name are a pair, a 3rd opens again. A pair is written at its closer's place, the
+ * forward read first (the opener, unless the strands differ and the closer is the forward one). mode_bits: what a base mismatch in the overlap does -
+ * precedence MAPQ > REMOVE > BASEQ > BASEN. ignore_indels: an indel within 4 bases of the clip position no longer sends the whole clip to one mate (to the
+ * reverse read when the number of soft-clipped pairs in front of the pair is even, else to the forward read; removed pairs count). A clipped record has pos,
+ * n_cigar_op, its CIGAR, next_pos and tlen rewritten and "BS:Z:<old CIGAR>" appended behind its tags; its bin field keeps the input's bytes. The names still open at the end are
+ * written in file order (the reference: QHash order). level: -1 (default) or 0 .. 9. counts: reads, saved, clipped, mismatch, bases, bases clipped (the first
+ * four are `int` in the reference; here 64-bit). The earliest error in file order stops the run: NGSQC_E_FORMAT with the reference's message and *err (may be
+ * null) filled: the ordinal of the closing record, the code and its two integers (CIGAR_CHAR, SC_OP, BAD_BASE: the character; LENGTH: the two list lengths -
+ * also where the reference reads behind the shorter list). A soft-clipped pair with a CG-tag CIGAR, or whose new CIGAR needs more than 65535 operations, is
+ * NGSQC_E_UNSUPPORTED (code UNSUPPORTED). ORIENT, SC_ORDER, SC_START and SC_END cannot be reached. A handle on a shard, a range or regions: NGSQC_E_ARG. */
+enum { NGSQC_CLIP_MAPQ = 1, NGSQC_CLIP_REMOVE = 2, NGSQC_CLIP_BASEQ = 4, NGSQC_CLIP_BASEN = 8 };
+enum { NGSQC_CLIPERR_NONE = 0, NGSQC_CLIPERR_ORIENT, NGSQC_CLIPERR_CIGAR_CHAR, NGSQC_CLIPERR_LENGTH, NGSQC_CLIPERR_SC_ORDER, NGSQC_CLIPERR_SC_START, NGSQC_CLIPERR_SC_END,
+       NGSQC_CLIPERR_SC_INDEX, NGSQC_CLIPERR_SC_OP, NGSQC_CLIPERR_BAD_BASE, NGSQC_CLIPERR_UNSUPPORTED };
+enum { NGSQC_CLIP_ROLE_PASS = 0, NGSQC_CLIP_ROLE_FORWARD = 1, NGSQC_CLIP_ROLE_REVERSE = 2, NGSQC_CLIP_ROLE_LEFTOVER = 3 };
+enum { NGSQC_CLIP_V_PAIR = 1, NGSQC_CLIP_V_MISMATCH = 2, NGSQC_CLIP_V_REMOVED = 4, NGSQC_CLIP_V_MAPQ0 = 8, NGSQC_CLIP_V_QUAL = 16, NGSQC_CLIP_V_BASES = 32, NGSQC_CLIP_V_REWRITTEN = 64 };
+typedef struct { int64_t record; int32_t code, a, b; } ngsqc_clip_error;
+int ngsqc_clip_overlap(ngsqc_handle* h, const char* out_bam_path, int32_t mode_bits, int32_t ignore_indels, int32_t level, int64_t* counts /* [6] */, ngsqc_clip_error* err);
+/* The plan of that tool on its own, no file written: six integers per record of the file in file order - the role (NGSQC_CLIP_ROLE_*), the bases clipped from
+ * this mate, the new pos, the new number of CIGAR operations, the new tlen, the verdict bits (NGSQC_CLIP_V_*; REWRITTEN: this mate was clipped). A record
+ * that is written as it is shows its own fields. cap_records: the rows plan holds; NGSQC_E_ARG when the file has more records. */
+int ngsqc_clip_overlap_plan(ngsqc_handle* h, int32_t mode_bits, int32_t ignore_indels, int32_t* plan /* [cap_records][6] */, int64_t cap_records, ngsqc_clip_error* err);
+
 /* ---- BamToFastq (src/BamToFastq/main.cpp:77-214): the records of the handle in file order, secondary and supplementary records skipped; with remove_duplicates
  * the duplicates skipped and counted; with fix a record whose (name, read 1) pair came earlier in the file dropped and counted (the set of seen pairs lives in
  * device memory for the whole run). Paired-end mode (out2 not NULL and not ""): unpaired records are skipped and counted, the others are joined by read name

@@ -130,6 +130,18 @@ class RmCounts(C.Structure):
     _fields_ = [(n, C.c_int64) for n in RM_COUNT_NAMES] + [("err_record", C.c_int64), ("err_code", C.c_int32), ("err_variant", C.c_int32)]
 
 
+CLIP_MAPQ, CLIP_REMOVE, CLIP_BASEQ, CLIP_BASEN = 1, 2, 4, 8
+CLIP_COUNT_NAMES = ("reads", "saved", "clipped", "mismatch", "bases", "bases_clipped")
+CLIP_PLAN_COLUMNS = ("role", "clipped", "pos", "n_cigar", "tlen", "verdict")
+(CLIPERR_NONE, CLIPERR_ORIENT, CLIPERR_CIGAR_CHAR, CLIPERR_LENGTH, CLIPERR_SC_ORDER, CLIPERR_SC_START, CLIPERR_SC_END, CLIPERR_SC_INDEX, CLIPERR_SC_OP, CLIPERR_BAD_BASE,
+ CLIPERR_UNSUPPORTED) = range(11)
+
+
+class ClipError(C.Structure):
+    """Where ngsqc_clip_overlap stopped (include/ngsqc.h ngsqc_clip_error)"""
+    _fields_ = [("record", C.c_int64), ("code", C.c_int32), ("a", C.c_int32), ("b", C.c_int32)]
+
+
 class JobResult(C.Structure):
     _fields_ = [("counters", C.c_void_p), ("gc_reads", C.c_void_p), ("site_counts", C.c_void_p), ("read_stats", C.c_void_p)]
 
@@ -214,6 +226,8 @@ def lib():
         L.ngsqc_match_names.restype = i32; L.ngsqc_match_names.argtypes = [vp, vp, vp, i64, vp, i64]
         L.ngsqc_remove_variants.restype = i32; L.ngsqc_remove_variants.argtypes = [vp, vp, i64, C.POINTER(RmParams), cp, C.POINTER(RmCounts)]
         L.ngsqc_variant_verdicts.restype = i32; L.ngsqc_variant_verdicts.argtypes = [vp, vp, i64, C.POINTER(RmParams), vp, i64]
+        L.ngsqc_clip_overlap.restype = i32; L.ngsqc_clip_overlap.argtypes = [vp, cp, i32, i32, i32, vp, C.POINTER(ClipError)]
+        L.ngsqc_clip_overlap_plan.restype = i32; L.ngsqc_clip_overlap_plan.argtypes = [vp, i32, i32, vp, i64, C.POINTER(ClipError)]
         L.ngsqc_scan_reads.restype = i32; L.ngsqc_scan_reads.argtypes = [vp, C.c_int32, C.POINTER(ReadStats)]
         L.ngsqc_read_length_hist.restype = i32; L.ngsqc_read_length_hist.argtypes = [vp, vp, i64]
         L.ngsqc_read_cycle_stats.restype = i32; L.ngsqc_read_cycle_stats.argtypes = [vp, vp, i64]
@@ -288,6 +302,7 @@ EXPORTS = [
     "ngsqc_set_reference", "ngsqc_set_cram_skip", "ngsqc_set_cram_skip_thread", "ngsqc_cram_to_bam", "ngsqc_indel_windows", "ngsqc_variant_details",
     "ngsqc_filter_pairs", "ngsqc_bgzf_compress", "ngsqc_bgzf_compress_level", "ngsqc_bam_to_fastq", "ngsqc_downsample", "ngsqc_downsample_keep",
     "ngsqc_extract_reads", "ngsqc_match_names", "ngsqc_remove_variants", "ngsqc_variant_verdicts",
+    "ngsqc_clip_overlap", "ngsqc_clip_overlap_plan",
 ]
 
 
@@ -733,6 +748,30 @@ class Handle:
         out = np.zeros(max(cap, 1), dtype=np.uint8)
         self._chk(lib().ngsqc_variant_verdicts(self.h, arr, n, C.byref(p), out.ctypes.data, cap))
         return out[:cap].tobytes()
+
+    def clip_overlap(self, out, mode=0, ignore_indels=False, level=-1):
+        """BamClipOverlap (src/BamClipOverlap/main.cpp) of the whole file into the BAM out (include/ngsqc.h ngsqc_clip_overlap): overlapping read pairs
+        soft-clipped, mode: CLIP_MAPQ / CLIP_REMOVE / CLIP_BASEQ / CLIP_BASEN for a mismatch in the overlap. Returns the counts as a dict (CLIP_COUNT_NAMES). An
+        error of a pair raises with the reference's message; the exception's clip_error holds (ordinal of the closing record, error code, its two integers)."""
+        cnt, err = np.zeros(6, dtype=np.int64), ClipError(-1, 0, 0, 0)
+        try:
+            self._chk(lib().ngsqc_clip_overlap(self.h, os.fsencode(out), int(mode), int(bool(ignore_indels)), int(level), cnt.ctypes.data, C.byref(err)))
+        except Exception as e:
+            e.clip_error = (int(err.record), int(err.code), int(err.a), int(err.b))
+            raise
+        return {k: int(v) for k, v in zip(CLIP_COUNT_NAMES, cnt)}
+
+    def clip_overlap_plan(self, mode=0, ignore_indels=False):
+        """The plan of BamClipOverlap on its own (include/ngsqc.h ngsqc_clip_overlap_plan): int32[n_records][6], per record of the file in file order the
+        columns CLIP_PLAN_COLUMNS. No file is written."""
+        cap = self.n_records
+        plan, err = np.zeros((max(cap, 1), 6), dtype=np.int32), ClipError(-1, 0, 0, 0)
+        try:
+            self._chk(lib().ngsqc_clip_overlap_plan(self.h, int(mode), int(bool(ignore_indels)), plan.ctypes.data, cap, C.byref(err)))
+        except Exception as e:
+            e.clip_error = (int(err.record), int(err.code), int(err.a), int(err.b))
+            raise
+        return plan[:cap]
 
     # ---- one BAM sharded over several handles (include/ngsqc.h, "sharded" section) ----
     def scan_mapping_partial(self, mode, **kw):

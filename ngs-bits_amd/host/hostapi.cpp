@@ -4,6 +4,7 @@
 #include "core.hpp"
 #include "Variant.hpp"
 #include "RmVariants.hpp"
+#include "ClipOverlap.hpp"
 #include <cstring>
 using namespace ngsbits;
 
@@ -84,5 +85,16 @@ long long ngsbits_rm_variants(const char* vcf_path, const char* const* ref_names
 		return (long long)t.lines.size();
 	}
 	catch (std::exception& e) { return fail(e, err, err_cap); }
+}
+
+// The three summary lines of BamClipOverlap for the counts of ngsqc_clip_overlap (host/ClipOverlap.hpp), as the tool prints them. Returns the length of the text
+// (also when it exceeds cap), -1 with the "Lost Reads" message in err when a read is missing.
+long long ngsbits_clip_summary(const long long* counts, char* out, long long cap, char* err, int err_cap)
+{
+	int64_t c[6]; for (int i = 0; i < 6; ++i) c[i] = counts[i];
+	std::string lost; const std::string text = clipSummary(c, lost);
+	if (!lost.empty()) { if (err && err_cap > 0) { strncpy(err, lost.c_str(), (size_t)err_cap - 1); err[err_cap - 1] = 0; } return -1; }
+	if (out && cap > 0) { strncpy(out, text.c_str(), (size_t)cap - 1); out[cap - 1] = 0; }
+	return (long long)text.size();
 }
 }
