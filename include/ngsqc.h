@@ -343,6 +343,19 @@ int ngsqc_extract_reads(ngsqc_handle* h, const void* names, const int32_t* name_
  * file order, is one of the listed names, else 0. No file is written. cap: the bytes match_out holds; NGSQC_E_ARG when the file has more records. */
 int ngsqc_match_names(ngsqc_handle* h, const void* names, const int32_t* name_len, int64_t n_names, uint8_t* match_out, int64_t cap);
 
+/* ---- BamCleanHaloplex (src/BamCleanHaloplex/main.cpp:27-69) over the same writer, without the join. Every record of the file is written, in file order, behind
+ * the input's header. A record is a candidate when it is none of unmapped (0x4), secondary (0x100), duplicate (0x400) or supplementary (0x800). A candidate whose
+ * CIGAR's M operations (op 0 alone: '=' and 'X' do not count) add up to less than min_match fails: 0x4 and 0x100 are set in its flag word, and nothing else of
+ * the record changes (bin, the mate fields and the tags are the input's). The CIGAR is the one htslib hands out: a record whose CIGAR sits in a CG:B,I tag is
+ * judged on the tag's operations and written as bam_write1 writes it. counts: the records, the candidates, the failed ones (`int` in the reference; 64-bit
+ * here, as is the sum of a CIGAR). The output is written as ngsqc_filter_pairs writes its output. NGSQC_E_ARG for a null pointer and for a handle on a shard, a
+ * range, regions or the first records. */
+typedef struct { int64_t reads, candidates, failed; } ngsqc_haloplex_counts;
+int ngsqc_clean_haloplex(ngsqc_handle* h, int32_t min_match, const char* out_bam_path, ngsqc_haloplex_counts* counts);
+/* The verdicts of that tool on their own (like ngsqc_match_names): out[i] for the i-th record of the file in file order: 0 not a candidate, 1 a candidate that
+ * is kept, 2 a candidate that fails. No file is written. cap: the bytes out holds; NGSQC_E_ARG when the file has more records. */
+int ngsqc_haloplex_verdicts(ngsqc_handle* h, int32_t min_match, uint8_t* out, int64_t cap);
+
 /* ---- BamRemoveVariants (src/BamRemoveVariants/main.cpp:34-278) over the same join and writer: read pairs that carry a variant of a VCF are dropped, or with
  * mask kept with the reference base put back. Records with flag 0x100 or 0x800 are counted as skipped and take no further part (:141-145); every other record
  * takes part. A table line overlaps a record when tid matches and [beg, end] meets [pos + 1, pos + max(1, reference length)] (the reference length is 0 with flag

@@ -10,7 +10,7 @@ from .capi import (  # noqa: F401
     IndelWindow, VariantParams, ALLELE_NONE, ALLELE_INS, ALLELE_DEL, INDEL_COUNTER_NAMES,
     PairFilter, bgzf_compress, FastqParams, FastqCounts, FASTQ_COUNT_NAMES,
     DownsampleParams, DownsampleCounts, DOWNSAMPLE_COUNT_NAMES, DOWNSAMPLE_CHUNK, downsample_keep,
-    ExtractCounts, EXTRACT_COUNT_NAMES,
+    ExtractCounts, EXTRACT_COUNT_NAMES, HaloplexCounts, HALOPLEX_COUNT_NAMES,
     RmVariant, RmParams, RmCounts, RM_COUNT_NAMES, RMVAR_SNV, RMVAR_OTHER, RMVAR_INVALID, RMERR_NONE, RMERR_INVALID_LINE, RMERR_POS_NOT_FOUND, RMERR_BAD_BASE,
     ClipError, CLIP_MAPQ, CLIP_REMOVE, CLIP_BASEQ, CLIP_BASEN, CLIP_COUNT_NAMES, CLIP_PLAN_COLUMNS, CLIPERR_NONE, CLIPERR_ORIENT, CLIPERR_CIGAR_CHAR, CLIPERR_LENGTH, CLIPERR_SC_ORDER,
     CLIPERR_SC_START, CLIPERR_SC_END, CLIPERR_SC_INDEX, CLIPERR_SC_OP, CLIPERR_BAD_BASE, CLIPERR_UNSUPPORTED,

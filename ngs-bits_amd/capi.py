@@ -112,6 +112,13 @@ class ExtractCounts(C.Structure):
     _fields_ = [(n, C.c_int64) for n in EXTRACT_COUNT_NAMES]
 
 
+HALOPLEX_COUNT_NAMES = ("reads", "candidates", "failed")
+
+
+class HaloplexCounts(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in HALOPLEX_COUNT_NAMES]
+
+
 RM_COUNT_NAMES = ("passed", "dropped", "modified", "skipped")
 RMVAR_SNV, RMVAR_OTHER, RMVAR_INVALID = 0, 1, 2
 RMERR_NONE, RMERR_INVALID_LINE, RMERR_POS_NOT_FOUND, RMERR_BAD_BASE = 0, 1, 2, 3
@@ -224,6 +231,8 @@ def lib():
         L.ngsqc_downsample_keep.restype = i32; L.ngsqc_downsample_keep.argtypes = [C.c_uint32, C.c_double, i64, i64, i32, vp]
         L.ngsqc_extract_reads.restype = i32; L.ngsqc_extract_reads.argtypes = [vp, vp, vp, i64, cp, cp, C.POINTER(ExtractCounts)]
         L.ngsqc_match_names.restype = i32; L.ngsqc_match_names.argtypes = [vp, vp, vp, i64, vp, i64]
+        L.ngsqc_clean_haloplex.restype = i32; L.ngsqc_clean_haloplex.argtypes = [vp, i32, cp, C.POINTER(HaloplexCounts)]
+        L.ngsqc_haloplex_verdicts.restype = i32; L.ngsqc_haloplex_verdicts.argtypes = [vp, i32, vp, i64]
         L.ngsqc_remove_variants.restype = i32; L.ngsqc_remove_variants.argtypes = [vp, vp, i64, C.POINTER(RmParams), cp, C.POINTER(RmCounts)]
         L.ngsqc_variant_verdicts.restype = i32; L.ngsqc_variant_verdicts.argtypes = [vp, vp, i64, C.POINTER(RmParams), vp, i64]
         L.ngsqc_clip_overlap.restype = i32; L.ngsqc_clip_overlap.argtypes = [vp, cp, i32, i32, i32, vp, C.POINTER(ClipError)]
@@ -302,7 +311,7 @@ EXPORTS = [
     "ngsqc_set_reference", "ngsqc_set_cram_skip", "ngsqc_set_cram_skip_thread", "ngsqc_cram_to_bam", "ngsqc_indel_windows", "ngsqc_variant_details",
     "ngsqc_filter_pairs", "ngsqc_bgzf_compress", "ngsqc_bgzf_compress_level", "ngsqc_bam_to_fastq", "ngsqc_downsample", "ngsqc_downsample_keep",
     "ngsqc_extract_reads", "ngsqc_match_names", "ngsqc_remove_variants", "ngsqc_variant_verdicts",
-    "ngsqc_clip_overlap", "ngsqc_clip_overlap_plan",
+    "ngsqc_clip_overlap", "ngsqc_clip_overlap_plan", "ngsqc_clean_haloplex", "ngsqc_haloplex_verdicts",
 ]
 
 
@@ -724,6 +733,22 @@ class Handle:
         out = np.zeros(max(cap, 1), dtype=np.uint8)
         self._chk(lib().ngsqc_match_names(self.h, buf, lens.ctypes.data, n, out.ctypes.data, cap))
         return out[:cap]
+
+    def clean_haloplex(self, out, min_match=30):
+        """BamCleanHaloplex (src/BamCleanHaloplex/main.cpp) of the whole file into the BAM out (include/ngsqc.h ngsqc_clean_haloplex): every record, the
+        candidates whose CIGAR's M lengths add up to less than min_match with 0x4 and 0x100 set in the flag word. Returns the counts as a dict
+        (HALOPLEX_COUNT_NAMES: records, candidates, failed)."""
+        cnt = HaloplexCounts()
+        self._chk(lib().ngsqc_clean_haloplex(self.h, int(min_match), os.fsencode(out), C.byref(cnt)))
+        return {k: int(getattr(cnt, k)) for k in HALOPLEX_COUNT_NAMES}
+
+    def haloplex_verdicts(self, min_match=30):
+        """The verdicts of BamCleanHaloplex on their own (include/ngsqc.h ngsqc_haloplex_verdicts): bytes, one per record of the file in file order: 0 not a
+        candidate, 1 kept, 2 failed."""
+        cap = self.n_records
+        out = np.zeros(max(cap, 1), dtype=np.uint8)
+        self._chk(lib().ngsqc_haloplex_verdicts(self.h, int(min_match), out.ctypes.data, cap))
+        return out[:cap].tobytes()
 
     def remove_variants(self, out, variants, mask=False, single_end=False, keep_indels=False):
         """BamRemoveVariants (src/BamRemoveVariants/main.cpp) of the whole file (include/ngsqc.h ngsqc_remove_variants): the read pairs (single_end: the reads)

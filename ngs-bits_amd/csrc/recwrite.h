@@ -1,5 +1,6 @@
 // The bytes BamWriter::writeAlignment writes for a record (src/cppNGS/BamWriter.cpp over htslib's bam_write1), shared by the tools that gather records into a
-// BAM output stream (BamFilter: pairs.hip, BamDownsample: downsample.hip): the size a record takes in the output and the wave-wide copy into a window.
+// BAM output stream (BamFilter: pairs.hip, BamDownsample: downsample.hip, and the writers after them): the size a record takes in the output and the wave-wide
+// copy into a window, with bits OR-ed into the copy's flag word where a tool asks for it (BamCleanHaloplex: haloplex.hip).
 #pragma once
 #include "join.h"
 
@@ -27,22 +28,30 @@ __device__ __forceinline__ bool cg_of(const RecView& r, CgInfo& g)
 	g.ops = e.cigar; g.n = e.n_cigar; g.tag = e.cigar - 8;
 	return true;
 }
+// e: r behind rec_apply_cg (a caller that needs the effective CIGAR anyway scans the tags once)
+__device__ __forceinline__ uint32_t out_size(const RecView& r, const RecView& e)
+{
+	if (e.cigar == r.cigar) return r.bs + 4;
+	return e.n_cigar <= 65535 ? r.bs + 4 - 4 * r.n_cigar_raw - 8 : r.bs + 4 - 4 * r.n_cigar_raw + 8;
+}
 __device__ __forceinline__ uint32_t out_size(const RecView& r)
 {
-	CgInfo g;
-	if (!cg_of(r, g)) return r.bs + 4;
-	return g.n <= 65535 ? r.bs + 4 - 4 * r.n_cigar_raw - 8 : r.bs + 4 - 4 * r.n_cigar_raw + 8;
+	RecView e = r; rec_apply_cg(e);
+	return out_size(r, e);
 }
 
-// one record into the output window at pos (wave-wide)
-__device__ void write_record(const uint8_t* __restrict__ s, const Win& w, int64_t pos, int lane)
+// one record into the output window at pos (wave-wide). flag_or: bits OR-ed into the flag word of the copy (bytes 18-19 of the record, block_size included); each
+// of the two bytes is stored by whoever stores that byte of the copy, and only where it lies inside the window: a record that straddles two windows gets its
+// low flag byte in one launch and its high one in the other. 0 (the default): the copy is the source's bytes
+__device__ void write_record(const uint8_t* __restrict__ s, const Win& w, int64_t pos, int lane, uint32_t flag_or = 0)
 {
 	const RecView r = load_rec(s, 0);
 	CgInfo g;
 	if (!cg_of(r, g))
 	{
 		const int64_t n = (int64_t)r.bs + 4, a = max<int64_t>(0, w.lo - pos), b = min<int64_t>(n, w.hi - pos);
-		for (int64_t i = a + lane; i < b; i += 64) w.base[pos + i] = s[i];
+		if (!flag_or) { for (int64_t i = a + lane; i < b; i += 64) w.base[pos + i] = s[i]; return; }
+		for (int64_t i = a + lane; i < b; i += 64) w.base[pos + i] = (uint8_t)(s[i] | (i == 18 ? flag_or : i == 19 ? flag_or >> 8 : 0u));
 		return;
 	}
 	if (lane) return;   // (rare: long reads only)
@@ -56,6 +65,7 @@ __device__ void write_record(const uint8_t* __restrict__ s, const Win& w, int64_
 	for (int i = 0; i < 36; ++i) fixed[i] = s[i];
 	for (int i = 0; i < 4; ++i) fixed[i] = (uint8_t)(bs >> (8 * i));
 	fixed[14] = (uint8_t)bin; fixed[15] = (uint8_t)(bin >> 8); fixed[16] = (uint8_t)nc; fixed[17] = (uint8_t)(nc >> 8);
+	fixed[18] |= (uint8_t)flag_or; fixed[19] |= (uint8_t)(flag_or >> 8);   // (put() keeps each byte to the window)
 	int64_t o = pos;
 	for (int i = 0; i < 36; ++i) put(w, o, fixed[i]);
 	for (uint32_t i = 0; i < r.l_name; ++i) put(w, o, s[36 + i]);

@@ -1,0 +1,105 @@
+"""The device's decision for a record of BamCleanHaloplex (ngs-bits_amd/csrc/haloplex_visit.h - the text the GPU library compiles into its verdict kernels) on the
+CPU, against the Python restatement: the verdict byte of every record, the M sum taken whole and as the 64 strided slices of a wave's lanes, the verdict as the
+two kernels split the work at HX_LANE_OPS, and the flag bytes of the written record - on the designed BAM (tests/haloplex_cases.py) and on every BAM under
+tests/golden/ref_in. Plain integer code: held here without a GPU."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import bamcleanhaloplex_oracle as O
+import haloplex_cases as K
+from conftest import ROOT
+
+EMUL = os.path.join(ROOT, "tests", "emul")
+CSRC = os.path.join(ROOT, "ngs-bits_amd", "csrc")
+GI = os.path.join(ROOT, "tests", "golden", "ref_in")
+GOLDEN = sorted(os.path.relpath(os.path.join(d, f), GI) for d, _, fs in os.walk(GI) for f in fs if f.endswith(".bam"))
+
+
+@pytest.fixture(scope="module")
+def lib():
+    so = os.path.join(EMUL, "libhaloplex.so")
+    srcs = [os.path.join(EMUL, "haloplex_emul.cpp"), os.path.join(CSRC, "haloplex_visit.h"), os.path.join(CSRC, "rec.h")]
+    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
+        subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-Wall", "-Wno-unknown-pragmas", "-Wno-unused-function", "-o", so, srcs[0]])
+    L = C.CDLL(so)
+    L.haloplex_lane_ops.restype = C.c_int32
+    L.haloplex_emul.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    return L
+
+
+def emulate(L, recs, min_match):
+    infl = np.frombuffer(b"".join(recs) + bytes(64), np.uint8)
+    off = np.cumsum([0] + [len(b) for b in recs[:-1]]).astype(np.int64) if recs else np.zeros(1, np.int64)
+    n = len(recs)
+    vd, cut = np.zeros(n + 1, np.uint8), np.zeros(n + 1, np.uint8)
+    whole, sliced = np.zeros(n + 1, np.int64), np.zeros(n + 1, np.int64)
+    patched = np.zeros(len(infl), np.uint8)
+    L.haloplex_emul(infl.ctypes.data, off.ctypes.data, n, min_match, vd.ctypes.data, whole.ctypes.data, sliced.ctypes.data, cut.ctypes.data, patched.ctypes.data)
+    out = [patched[o:o + len(b)].tobytes() for o, b in zip(off, recs)]
+    return vd[:n].tobytes(), whole[:n].tolist(), sliced[:n].tolist(), cut[:n].tobytes(), out
+
+
+def check(L, recs, min_matches):
+    parsed = [O.Rec(b) for b in recs]
+    sums = [-1 if r.flag & O.EXCLUDING else O.sum_m(r) for r in parsed]
+    for k, mm in enumerate(min_matches):
+        exp = bytes(O.NOT_CANDIDATE if s < 0 else O.FAILED if s < mm else O.KEPT for s in sums)   # (O.verdict with the record parsed once)
+        if k == 0 or len(recs) < 2000:
+            assert exp == O.verdicts(recs, mm)
+        vd, whole, sliced, cut, out = emulate(L, recs, mm)
+        assert vd == exp, (mm, [i for i in range(len(recs)) if vd[i] != exp[i]][:10])
+        assert cut == exp, (mm, [i for i in range(len(recs)) if cut[i] != exp[i]][:10])
+        assert whole == sums and sliced == sums, mm
+        for i, b in enumerate(recs):
+            assert out[i] == O.with_flags(b, O.FAIL_FLAGS if exp[i] == O.FAILED else 0), (mm, i)
+    return sums
+
+
+def test_threshold_is_the_designed_one(lib):
+    assert lib.haloplex_lane_ops() == K.T and 16 <= K.T <= 64 and K.T & (K.T - 1) == 0
+
+
+def test_designed_records(lib):
+    recs, labels = K.designed()
+    sums = check(lib, recs, K.MIN_MATCHES)
+    vd = O.verdicts(recs, K.MIN_MATCH)
+    # the design holds what it claims: every count of operations with a record just passing and one just failing, the excluded flags, the CG records both ways
+    for n in K.LONG_COUNTS:
+        p, f = labels["ops%d-pass" % n], labels["ops%d-fail" % n]
+        assert O.Rec(recs[p]).n_cigar == O.Rec(recs[f]).n_cigar == n and (sums[p], sums[f]) == (K.MIN_MATCH, K.MIN_MATCH - 1) and (vd[p], vd[f]) == (O.KEPT, O.FAILED)
+        assert O.Rec(recs[p]).cigar[-1] == 1 << 4 and O.Rec(recs[p]).cigar[0] == 1 << 4   # (1M at both ends: a dropped first or last operation changes the verdict)
+    for fl in (0x4, 0x100, 0x400, 0x800, 0xD04):
+        assert vd[labels["flag%x" % fl]] == O.NOT_CANDIDATE
+    assert [sums[labels[k]] for k in ("m29", "m30", "m31", "nocigar", "nocigar-seq", "eqx", "split-pass", "split-fail", "mixed-fail", "mixed-pass")] == [29, 30, 31, 0, 0, 0, 30, 29, 29, 30]
+    a, b = O.Rec(recs[labels["cg-tag-fails"]]), O.Rec(recs[labels["cg-tag-passes"]])
+    assert a.cg() and b.cg() and sum(c >> 4 for c in a.cigar if c & 15 == 0) == 40 and sum(c >> 4 for c in b.cigar if c & 15 == 0) == 0
+    assert (vd[labels["cg-tag-fails"]], vd[labels["cg-tag-passes"]]) == (O.FAILED, O.KEPT)
+    assert O.Rec(recs[labels["cg-unplaced"]]).cg() is None and vd[labels["cg-unplaced"]] == O.FAILED
+    assert (vd[labels["cg200-pass"]], vd[labels["cg200-fail"]], vd[labels["cg33-pass"]], vd[labels["cg33-fail"]]) == (O.KEPT, O.FAILED, O.KEPT, O.FAILED)
+    assert not any(v == O.FAILED for v in O.verdicts(recs, 0)) and 200 < len(recs) < 1000
+
+
+def test_window_edge_records_sit_where_designed():
+    recs, labels = K.designed()
+    _, out, _ = O.clean(recs, K.MIN_MATCH)
+    starts = np.cumsum([0] + [len(b) for b in out])
+    for label, in_front in (("edge-18|19", 19), ("edge-17|18", 18), ("edge-19|20", 20), ("edge-cg-18|19", 19)):
+        i = labels[label]
+        assert (int(starts[i]) + in_front) % K.EDGE == 0 and O.verdict(recs[i], K.MIN_MATCH) == O.FAILED, label
+        assert out[i][18:20] != O.written(O.Rec(recs[i]))[18:20]
+
+
+def test_more_than_65535_operations(lib):
+    recs = K.designed_big()
+    assert len(O.Rec(recs[1]).cg()[0]) == 65540
+    assert check(lib, recs, (0, 30, 32770, 32771, 2 ** 31 - 1)) == [10, 32770, 40]
+
+
+@pytest.mark.parametrize("bam", GOLDEN)
+def test_golden_bams(lib, bam):
+    _, recs = O.read_bam(os.path.join(GI, bam))
+    check(lib, recs, (0, 1, 30, 100))
