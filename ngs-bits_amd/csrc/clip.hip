@@ -172,28 +172,16 @@ __global__ __launch_bounds__(256) void clip_left_sizes_kernel(const uint64_t* __
 	const int64_t stride = (int64_t)gridDim.x * blockDim.x;
 	for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) sz[i] = out_size(load_rec((const uint8_t*)(uintptr_t)src[i], 0));
 }
-__global__ __launch_bounds__(256) void clip_left_gather_kernel(const uint64_t* __restrict__ src, const uint64_t* __restrict__ sz, const uint64_t* __restrict__ off, int64_t n, int64_t ws, Win w)
-{
-	const int lane = threadIdx.x & 63;
-	const int64_t nw = ((int64_t)gridDim.x * blockDim.x) >> 6;
-	for (int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6; i < n; i += nw)
-	{
-		const int64_t pos = (int64_t)off[i] - ws;
-		if (pos >= w.hi || pos + (int64_t)sz[i] <= w.lo) continue;
-		write_record((const uint8_t*)(uintptr_t)src[i], w, pos, lane);
-	}
-}
 
 // the reference's message for the pair that the record with ordinal `ord` of the resident tile closes
 [[noreturn]] void throw_pair_error(const TileCtx& c, const int64_t* rec, int64_t ord, const int32_t* err_dev, ngsqc_clip_error* out, hipStream_t s)
 {
 	const int64_t i = ord - c.ord_base;
 	if (i < 0 || i >= c.n_rec) throw std::runtime_error("BamClipOverlap: the failing record is not in the resident tile");
-	int32_t e[3] = {0, 0, 0}; int64_t ro = 0; uint8_t head[36 + 256] = {0};
-	HIPCHK(hipMemcpyAsync(e, err_dev + 3 * i, sizeof(e), hipMemcpyDeviceToHost, s)); HIPCHK(hipMemcpyAsync(&ro, rec + i, 8, hipMemcpyDeviceToHost, s)); HIPCHK(hipStreamSynchronize(s));
-	HIPCHK(hipMemcpyAsync(head, c.infl + ro, (size_t)std::min<int64_t>((int64_t)sizeof(head), c.total - ro), hipMemcpyDeviceToHost, s)); HIPCHK(hipStreamSynchronize(s));
+	int32_t e[3] = {0, 0, 0};
+	HIPCHK(hipMemcpyAsync(e, err_dev + 3 * i, sizeof(e), hipMemcpyDeviceToHost, s));
+	const std::string name = fetch_rec_head(c, rec, i, s).name;   // (waits for the stream)
 	if (out) *out = ngsqc_clip_error{ord, e[0], e[1], e[2]};
-	const std::string name((const char*)head + 36, strnlen((const char*)head + 36, head[12]));
 	const std::string ch(1, (char)e[1]);
 	switch (e[0])
 	{
@@ -214,7 +202,7 @@ __global__ __launch_bounds__(256) void clip_left_gather_kernel(const uint64_t* _
 void clip_run(ngsqc_handle* h, const char* out_path, int mode, int ignore_indels, int level, int64_t* counts_out, ngsqc_clip_error* err_out, int32_t* plan_out, int64_t plan_cap)
 {
 	const char* T = "BamClipOverlap";
-	if (h->selection || h->n_shards != 1 || h->shard_own_members >= 0) throw ArgError("BamClipOverlap needs a handle on the whole file (not a shard, a range or regions)");
+	require_whole_file(h, T);
 	if (mode & ~(MODE_MAPQ | MODE_REMOVE | MODE_BASEQ | MODE_BASEN)) throw ArgError("unknown mode bits");
 	if (level < -1 || level > 9) throw ArgError("the compression level is -1 (the default) or 0 .. 9");
 	if (err_out) *err_out = ngsqc_clip_error{-1, 0, 0, 0};
@@ -229,27 +217,10 @@ void clip_run(ngsqc_handle* h, const char* out_path, int mode, int ignore_indels
 	DevBuf<unsigned long long> counts; counts.alloc(C_N);
 	HIPCHK(hipMemsetAsync(counts.p, 0, C_N * sizeof(unsigned long long), s)); HIPCHK(hipMemsetAsync(counts.p + C_ERR_ORD, 0xff, sizeof(unsigned long long), s));
 	if (plan_out) { grow(plan, (size_t)(6 * plan_cap) + 6, "the plan", T); if (plan_cap) HIPCHK(hipMemsetAsync(plan.p, 0, (size_t)(6 * plan_cap) * sizeof(int32_t), s)); }
-	if (write)
-	{
-		// the header: the input's bytes (magic, l_text, text, n_ref, refs), in members of its own (BamWriter::writeHeader copies the input's)
-		std::vector<uint8_t> hdr;
-		auto put32 = [&](uint32_t v) { for (int i = 0; i < 4; ++i) hdr.push_back((uint8_t)(v >> (8 * i))); };
-		hdr.insert(hdr.end(), {'B', 'A', 'M', 1}); put32((uint32_t)h->header_text.size()); hdr.insert(hdr.end(), h->header_text.begin(), h->header_text.end());
-		put32((uint32_t)h->ref_names.size());
-		for (size_t i = 0; i < h->ref_names.size(); ++i) { put32((uint32_t)h->ref_names[i].size() + 1); hdr.insert(hdr.end(), h->ref_names[i].begin(), h->ref_names[i].end()); hdr.push_back(0); put32((uint32_t)h->ref_lens[i]); }
-		out.sink.open(out_path, std::string("Could not open BAM/CRAM file for writing: ") + out_path);
-		for (size_t o = 0; o < hdr.size(); o += (size_t)W)
-		{
-			const size_t k = std::min(hdr.size() - o, (size_t)W);
-			out.ensure_obuf((int64_t)k, s);
-			HIPCHK(hipMemcpyAsync(out.obuf.p, hdr.data() + o, k, hipMemcpyHostToDevice, s));
-			out.deflate_out((int64_t)k, s, h->device);
-		}
-	}
+	if (write) open_bam(out, out_path, h, s);
 	StageClock ck_join(timing, s), ck_plan(timing, s), ck_gather(timing, s);
 	int64_t n_reads = 0; uint64_t clipped_pairs = 0;
-	const bool lazy_keep = h->lazy_recoff; h->lazy_recoff = false;
-	struct Restore { ngsqc_handle* h; bool v; ~Restore() { h->lazy_recoff = v; } } restore{h, lazy_keep};
+	EagerRecoff eager(h);
 	stream_tiles(h, [&](const TileCtx& c) {
 		const int64_t n = c.n_rec, H = j.H, N = H + n;
 		const int64_t* rec = n ? ensure_recoff(h) : nullptr;
@@ -264,35 +235,29 @@ void clip_run(ngsqc_handle* h, const char* out_path, int mode, int ignore_indels
 		hipLaunchKernelGGL(clip_keys_kernel, dim3(grid_for(N)), dim3(256), 0, s, c.infl, rec, n, H, c.ord_base, mask, j.key.p, j.val.p, j.src.p, j.info.p, jn.p, counts.p, plan.p, plan_out ? plan_cap : 0); KCHECK();
 		j.sort_resolve(n, s);
 		ck_join.mark();
-		uint64_t tot[2] = {0, 0}, ptot[2] = {0, 0}; unsigned long long err_ord = ~0ull;
+		uint64_t ptot[2] = {0, 0}; unsigned long long err_ord = ~0ull;
 		if (n)
 		{
 			ck_plan.mark();
 			hipLaunchKernelGGL(clip_flags_kernel, dim3(grid_for(n)), dim3(256), 0, s, j.close_of.p, j.src.p, n, H, flag.p); KCHECK();
-			size_t sb = j.tmp.n;
-			if (rocprim::exclusive_scan(j.tmp.p, sb, flag.p, par.p, clipped_pairs, (size_t)n, rocprim::plus<uint64_t>(), s) != hipSuccess) throw std::runtime_error("rocprim::exclusive_scan failed");
+			scan_u64(j.tmp, flag.p, par.p, clipped_pairs, (size_t)n, s);
 			hipLaunchKernelGGL(clip_plan_kernel, dim3(grid_for(n)), dim3(256), 0, s, j.close_of.p, jn.p, par.p, j.src.p, j.info.p, n, H, c.ord_base, mode, ignore_indels, sz.p, err.p, counts.p,
 			                   plan.p, plan_out ? plan_cap : 0); KCHECK();
 			ck_plan.mark();
-			sb = j.tmp.n;
-			if (rocprim::exclusive_scan(j.tmp.p, sb, sz.p, off.p, (uint64_t)(out.ws + out.carry), (size_t)n, rocprim::plus<uint64_t>(), s) != hipSuccess) throw std::runtime_error("rocprim::exclusive_scan failed");
-			HIPCHK(hipMemcpyAsync(&tot[0], off.p + n - 1, 8, hipMemcpyDeviceToHost, s)); HIPCHK(hipMemcpyAsync(&tot[1], sz.p + n - 1, 8, hipMemcpyDeviceToHost, s));
+			out.place(j.tmp, sz.p, off.p, n, s);
 			HIPCHK(hipMemcpyAsync(&ptot[0], par.p + n - 1, 8, hipMemcpyDeviceToHost, s)); HIPCHK(hipMemcpyAsync(&ptot[1], flag.p + n - 1, 8, hipMemcpyDeviceToHost, s));
 			HIPCHK(hipMemcpyAsync(&err_ord, counts.p + C_ERR_ORD, 8, hipMemcpyDeviceToHost, s));
 		}
-		j.keep_open(n, s);   // (waits for the stream: tot, ptot and err_ord are on the host)
+		j.keep_open(n, s);   // (waits for the stream: the placed end, ptot and err_ord are on the host)
 		if (err_ord != ~0ull) throw_pair_error(c, rec, (int64_t)err_ord, err.p, err_out, s);
 		if (n) clipped_pairs = ptot[0] + ptot[1];
 		if (write)
-		{
-			const int64_t out_end = n ? (int64_t)(tot[0] + tot[1]) : out.ws + out.carry;
-			out.emit(out_end, s, h->device, [&](const Win& win, int64_t ws) {
+			out.emit(out.placed_end(n), s, h->device, [&](const Win& win, int64_t ws) {
 				if (!n) return;
 				ck_gather.mark();
 				hipLaunchKernelGGL(clip_gather_kernel, dim3(grid_for(n, 4)), dim3(256), 0, s, j.close_of.p, jn.p, par.p, sz.p, off.p, n, H, j.src.p, mode, ignore_indels, ws, win); KCHECK();
 				ck_gather.mark();
 			});
-		}
 		HIPCHK(hipStreamSynchronize(s));   // (the old pool and the tile's bytes are no longer read)
 		j.end_tile();
 		return true;
@@ -310,27 +275,17 @@ void clip_run(ngsqc_handle* h, const char* out_path, int mode, int ignore_indels
 		tb = j.tmp.n;
 		if (rocprim::radix_sort_pairs(j.tmp.p, tb, j.hi.p, okey.p, j.hs.p, lsrc.p, (size_t)L, 0, 32, s) != hipSuccess) throw std::runtime_error("rocprim::radix_sort_pairs failed");
 		grow(sz, (size_t)L + 1, "the open names", T); grow(off, (size_t)L + 1, "the open names", T);
-		size_t sb = 0;
-		(void)rocprim::exclusive_scan(nullptr, sb, sz.p, off.p, (uint64_t)0, (size_t)L, rocprim::plus<uint64_t>(), s);
-		grow(j.tmp, sb + 16, "the open names", T);
+		grow(j.tmp, scan_tmp_bytes((size_t)L, s) + 16, "the open names", T);
 		hipLaunchKernelGGL(clip_left_sizes_kernel, dim3(grid_for(L)), dim3(256), 0, s, lsrc.p, L, sz.p); KCHECK();
-		sb = j.tmp.n;
-		if (rocprim::exclusive_scan(j.tmp.p, sb, sz.p, off.p, (uint64_t)(out.ws + out.carry), (size_t)L, rocprim::plus<uint64_t>(), s) != hipSuccess) throw std::runtime_error("rocprim::exclusive_scan failed");
-		uint64_t tot[2] = {0, 0};
-		HIPCHK(hipMemcpyAsync(&tot[0], off.p + L - 1, 8, hipMemcpyDeviceToHost, s)); HIPCHK(hipMemcpyAsync(&tot[1], sz.p + L - 1, 8, hipMemcpyDeviceToHost, s)); HIPCHK(hipStreamSynchronize(s));
-		out.emit((int64_t)(tot[0] + tot[1]), s, h->device, [&](const Win& win, int64_t ws) {
-			hipLaunchKernelGGL(clip_left_gather_kernel, dim3(grid_for(L, 4)), dim3(256), 0, s, lsrc.p, sz.p, off.p, L, ws, win); KCHECK();
-		});
+		out.place(j.tmp, sz.p, off.p, L, s);
+		HIPCHK(hipStreamSynchronize(s));
+		out.emit(out.placed_end(L), s, h->device, [&](const Win& win, int64_t ws) { launch_gather<false>(FromPtrs{lsrc.p}, NoMask{}, sz.p, off.p, L, ws, win, s); });
 		HIPCHK(hipStreamSynchronize(s));
 	}
 	unsigned long long jc[4] = {0, 0, 0, 0}, dc[C_N];
 	j.read_counts(jc, s);
 	HIPCHK(hipMemcpyAsync(dc, counts.p, sizeof(dc), hipMemcpyDeviceToHost, s)); HIPCHK(hipStreamSynchronize(s));
-	if (write)
-	{
-		out.finish(s, h->device);
-		if (!out.sink.err.empty()) throw IoError(std::string("Could not write BAM file ") + out_path + ": " + out.sink.err);
-	}
+	if (write) out.close(s, h->device, out_path);
 	if (plan_out && n_reads) { HIPCHK(hipMemcpyAsync(plan_out, plan.p, (size_t)(6 * n_reads) * sizeof(int32_t), hipMemcpyDeviceToHost, s)); HIPCHK(hipStreamSynchronize(s)); }
 	if (counts_out)
 	{

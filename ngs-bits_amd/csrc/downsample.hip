@@ -243,20 +243,13 @@ void downsample(ngsqc_handle* h, const ngsqc_downsample_params* dp, const char* 
 	const bool names = dp->want_names != 0;
 	if (names && !kept_names) throw ArgError("null argument");
 	if (!percentage_ok(dp->percentage)) { char b[64]; snprintf(b, sizeof(b), "%g", dp->percentage); throw ArgError(std::string("Invalid percentage ") + b + "!"); }
-	if (h->selection || h->n_shards != 1 || h->shard_own_members >= 0) throw ArgError("BamDownsample needs a handle on the whole file (not a shard, a range or regions)");
 	const char* T = "BamDownsample";
+	require_whole_file(h, T);
 	const uint64_t mask = name_hash_mask(h->sw.name_hash_bits);
 	const bool timing = h->sw.timing;
 	hipStream_t s = h->stream;
-	// the header: the input's bytes (magic, l_text, text, n_ref, refs), in members of its own
-	std::vector<uint8_t> hdr;
-	auto put32 = [&](uint32_t v) { for (int i = 0; i < 4; ++i) hdr.push_back((uint8_t)(v >> (8 * i))); };
-	hdr.insert(hdr.end(), {'B', 'A', 'M', 1}); put32((uint32_t)h->header_text.size()); hdr.insert(hdr.end(), h->header_text.begin(), h->header_text.end());
-	put32((uint32_t)h->ref_names.size());
-	for (size_t i = 0; i < h->ref_names.size(); ++i) { put32((uint32_t)h->ref_names[i].size() + 1); hdr.insert(hdr.end(), h->ref_names[i].begin(), h->ref_names[i].end()); hdr.push_back(0); put32((uint32_t)h->ref_lens[i]); }
 	const int64_t W = write_window_bytes(h->sw.write_window_pieces);
 	BgzfStream out(T, W, -1);
-	out.sink.open(out_path, std::string("Could not open BAM/CRAM file for writing: ") + out_path);
 	NameJoin j(T, s);
 	KeepGen gen(T, dp->seed, dp->percentage, 0);
 	DevBuf<uint64_t> dec, ord, sz, off, nsz, noff; DevBuf<uint8_t> se, nbuf;
@@ -264,15 +257,8 @@ void downsample(ngsqc_handle* h, const ngsqc_downsample_params* dp, const char* 
 	std::string name_lines;
 	int64_t K = 0;   // decisions of the tiles so far: the stream ordinal of the tile's first decision
 	double ms_join = 0, ms_keep = 0, t_w = wall_ms();
-	for (size_t o = 0; o < hdr.size(); o += (size_t)W)   // (the header's pieces are cut from its own start: windows are whole pieces)
-	{
-		const size_t k = std::min(hdr.size() - o, (size_t)W);
-		out.ensure_obuf((int64_t)k, s);
-		HIPCHK(hipMemcpyAsync(out.obuf.p, hdr.data() + o, k, hipMemcpyHostToDevice, s));
-		out.deflate_out((int64_t)k, s, h->device);
-	}
-	const bool lazy_keep = h->lazy_recoff; h->lazy_recoff = false;
-	struct Restore { ngsqc_handle* h; bool v; ~Restore() { h->lazy_recoff = v; } } restore{h, lazy_keep};
+	open_bam(out, out_path, h, s);
+	EagerRecoff eager(h);
 	stream_tiles(h, [&](const TileCtx& c) {
 		const double t0 = wall_ms();
 		const int64_t n = c.n_rec, H = j.H, N = H + n;
@@ -284,14 +270,13 @@ void downsample(ngsqc_handle* h, const ngsqc_downsample_params* dp, const char* 
 		if (N == 0) return true;
 		hipLaunchKernelGGL(ds_keys_kernel, dim3(grid_for(N)), dim3(256), 0, s, c.infl, rec, n, H, mask, j.key.p, j.val.p, j.src.p, j.info.p, se.p); KCHECK();
 		j.sort_resolve(n, s);
-		uint64_t tot[2] = {0, 0}, ntot[2] = {0, 0};
+		uint64_t ntot[2] = {0, 0};
 		if (n)
 		{
 			// the stream ordinals of the tile's deciding records, and their decisions
 			uint64_t m2[2] = {0, 0};
 			hipLaunchKernelGGL(ds_decides_kernel, dim3(grid_for(n)), dim3(256), 0, s, j.close_of.p, se.p, n, dec.p); KCHECK();
-			size_t sb = j.tmp.n;
-			if (rocprim::exclusive_scan(j.tmp.p, sb, dec.p, ord.p, (uint64_t)0, (size_t)n, rocprim::plus<uint64_t>(), s) != hipSuccess) throw std::runtime_error("rocprim::exclusive_scan failed");
+			scan_u64(j.tmp, dec.p, ord.p, 0, (size_t)n, s);
 			HIPCHK(hipMemcpyAsync(&m2[0], ord.p + n - 1, 8, hipMemcpyDeviceToHost, s)); HIPCHK(hipMemcpyAsync(&m2[1], dec.p + n - 1, 8, hipMemcpyDeviceToHost, s));
 			HIPCHK(hipStreamSynchronize(s));
 			const int64_t m = (int64_t)(m2[0] + m2[1]);
@@ -302,18 +287,14 @@ void downsample(ngsqc_handle* h, const ngsqc_downsample_params* dp, const char* 
 			                   sz.p, names ? nsz.p : nullptr, counts.p); KCHECK();
 			K += m;
 			// the output of the tile's kept records, behind the carried partial piece
-			sb = j.tmp.n;
-			if (rocprim::exclusive_scan(j.tmp.p, sb, sz.p, off.p, (uint64_t)(out.ws + out.carry), (size_t)n, rocprim::plus<uint64_t>(), s) != hipSuccess) throw std::runtime_error("rocprim::exclusive_scan failed");
-			HIPCHK(hipMemcpyAsync(&tot[0], off.p + n - 1, 8, hipMemcpyDeviceToHost, s)); HIPCHK(hipMemcpyAsync(&tot[1], sz.p + n - 1, 8, hipMemcpyDeviceToHost, s));
+			out.place(j.tmp, sz.p, off.p, n, s);
 			if (names)
 			{
-				sb = j.tmp.n;
-				if (rocprim::exclusive_scan(j.tmp.p, sb, nsz.p, noff.p, (uint64_t)0, (size_t)n, rocprim::plus<uint64_t>(), s) != hipSuccess) throw std::runtime_error("rocprim::exclusive_scan failed");
+				scan_u64(j.tmp, nsz.p, noff.p, 0, (size_t)n, s);
 				HIPCHK(hipMemcpyAsync(&ntot[0], noff.p + n - 1, 8, hipMemcpyDeviceToHost, s)); HIPCHK(hipMemcpyAsync(&ntot[1], nsz.p + n - 1, 8, hipMemcpyDeviceToHost, s));
 			}
 		}
-		j.keep_open(n, s);   // (waits for the stream: tot and ntot are on the host)
-		const int64_t out_end = n ? (int64_t)(tot[0] + tot[1]) : out.ws + out.carry;   // (stream position)
+		j.keep_open(n, s);   // (waits for the stream: the placed end and ntot are on the host)
 		const size_t nb = (size_t)(ntot[0] + ntot[1]), nl0 = name_lines.size();
 		if (nb)
 		{
@@ -324,7 +305,7 @@ void downsample(ngsqc_handle* h, const ngsqc_downsample_params* dp, const char* 
 		}
 		// the tile's records in windows of the stream
 		const double dz0 = out.ms_deflate + out.ms_copy;
-		out.emit(out_end, s, h->device, [&](const Win& win, int64_t ws) {
+		out.emit(out.placed_end(n), s, h->device, [&](const Win& win, int64_t ws) {
 			if (n) { hipLaunchKernelGGL(ds_gather_kernel, dim3(grid_for(n, 4)), dim3(256), 0, s, j.close_of.p, se.p, sz.p, off.p, n, H, j.src.p, j.info.p, ws, win); KCHECK(); }
 		});
 		HIPCHK(hipStreamSynchronize(s));   // (the old pool and the tile's bytes are no longer read)
@@ -335,8 +316,7 @@ void downsample(ngsqc_handle* h, const ngsqc_downsample_params* dp, const char* 
 	unsigned long long jc[4] = {0, 0, 0, 0}, dc[N_DS_COUNTS] = {0, 0, 0};
 	j.read_counts(jc, s);
 	HIPCHK(hipMemcpyAsync(dc, counts.p, sizeof(dc), hipMemcpyDeviceToHost, s)); HIPCHK(hipStreamSynchronize(s));
-	out.finish(s, h->device);
-	if (!out.sink.err.empty()) throw IoError(std::string("Could not write BAM file ") + out_path + ": " + out.sink.err);
+	out.close(s, h->device, out_path);
 	cnt->se = (int64_t)dc[C_SE]; cnt->se_written = (int64_t)dc[C_SE_PASS]; cnt->pe = (int64_t)(jc[0] + jc[1]); cnt->pe_written = (int64_t)dc[C_PE_PASS]; cnt->pe_unmatched = j.H;
 	if (names)
 	{

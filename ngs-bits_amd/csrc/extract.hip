@@ -13,7 +13,7 @@
 //      hashed with join.h's name_hash (NGSQC_NAME_HASH_BITS truncates it) and probed. A match byte, and the record's output size (recwrite.h) in the size array
 //      of its stream, 0 in the other; the two counts are one atomic add per wave.
 //   2. two exclusive scans (rocPRIM), each from its stream's position behind the carried partial piece.
-//   3. gather: one wave per record through recwrite.h's write_record into the stream's window, per stream; the whole pieces go through the encoder.
+//   3. gather: one wave per record of the stream (recwrite.h's gather_kernel) into the stream's window, per stream; the whole pieces go through the encoder.
 // Every record is a candidate: secondary, supplementary and unmapped records are looked up and written like any other (:64-76).
 #include "recwrite.h"
 #include <unordered_set>
@@ -98,21 +98,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void e
 	if ((threadIdx.x & 63) == 0) { if (w1) atomicAdd(&counts[0], w1); if (w2) atomicAdd(&counts[1], w2); }
 }
 
-// one stream's records of the tile into its window. off: absolute stream position of every record of the stream; ws: the stream position of obuf[0]
-__global__ __launch_bounds__(256) void ex_gather_kernel(const uint8_t* __restrict__ infl, const int64_t* __restrict__ recoff, const uint64_t* __restrict__ sz, const uint64_t* __restrict__ off,
-                                                        int64_t n, int64_t ws, Win w)
-{
-	const int lane = threadIdx.x & 63;
-	const int64_t nw = ((int64_t)gridDim.x * blockDim.x) >> 6;
-	for (int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6; i < n; i += nw)
-	{
-		if (!sz[i]) continue;
-		const int64_t pos = (int64_t)off[i] - ws;
-		if (pos >= w.hi || pos + (int64_t)sz[i] <= w.lo) continue;
-		write_record(infl + recoff[i], w, pos, lane);
-	}
-}
-
 // the set of the listed names on the device
 struct NameSet
 {
@@ -164,18 +149,6 @@ void check_names(const void* names, const int32_t* name_len, int64_t n_names)
 	if (n_names < 0) throw ArgError("negative number of read names");
 	if (n_names && (!names || !name_len)) throw ArgError("null argument");
 }
-
-void whole_file_only(const ngsqc_handle* h)
-{
-	if (h->selection || h->n_shards != 1 || h->shard_own_members >= 0) throw ArgError("BamExtract needs a handle on the whole file (not a shard, a range or regions)");
-}
-
-size_t scan_tmp_bytes(DevBuf<uint64_t>& a, DevBuf<uint64_t>& b, size_t n, hipStream_t s)
-{
-	size_t sb = 0;
-	(void)rocprim::exclusive_scan(nullptr, sb, a.p, b.p, (uint64_t)0, n, rocprim::plus<uint64_t>(), s);
-	return sb;
-}
 } // namespace
 
 namespace lib {
@@ -183,7 +156,7 @@ void extract_reads(ngsqc_handle* h, const void* names, const int32_t* name_len, 
 {
 	if (!out_path || !cnt) throw ArgError("null argument");
 	check_names(names, name_len, n_names);
-	whole_file_only(h);
+	require_whole_file(h, "BamExtract");
 	const char* T = "BamExtract";
 	const bool two = out2_path && *out2_path;
 	const uint64_t mask = name_hash_mask(h->sw.name_hash_bits);
@@ -193,32 +166,17 @@ void extract_reads(ngsqc_handle* h, const void* names, const int32_t* name_len, 
 	NameSet set;
 	set.build(T, (const uint8_t*)names, name_len, n_names, mask, s);
 	const NameTable table = set.table(mask);
-	// the header: the input's bytes (magic, l_text, text, n_ref, refs), in members of its own, into every output
-	std::vector<uint8_t> hdr;
-	auto put32 = [&](uint32_t v) { for (int i = 0; i < 4; ++i) hdr.push_back((uint8_t)(v >> (8 * i))); };
-	hdr.insert(hdr.end(), {'B', 'A', 'M', 1}); put32((uint32_t)h->header_text.size()); hdr.insert(hdr.end(), h->header_text.begin(), h->header_text.end());
-	put32((uint32_t)h->ref_names.size());
-	for (size_t i = 0; i < h->ref_names.size(); ++i) { put32((uint32_t)h->ref_names[i].size() + 1); hdr.insert(hdr.end(), h->ref_names[i].begin(), h->ref_names[i].end()); hdr.push_back(0); put32((uint32_t)h->ref_lens[i]); }
 	const int64_t W = write_window_bytes(h->sw.write_window_pieces);
 	BgzfStream o1(T, W, -1), o2(T, W, -1);
 	BgzfStream* outs[2] = {&o1, &o2};
 	const int n_out = two ? 2 : 1;
-	o1.sink.open(out_path, std::string("Could not open BAM/CRAM file for writing: ") + out_path);
-	if (two) o2.sink.open(out2_path, std::string("Could not open BAM/CRAM file for writing: ") + out2_path);
-	for (int k = 0; k < n_out; ++k)
-		for (size_t o = 0; o < hdr.size(); o += (size_t)W)   // (the header's pieces are cut from its own start: windows are whole pieces)
-		{
-			const size_t b = std::min(hdr.size() - o, (size_t)W);
-			outs[k]->ensure_obuf((int64_t)b, s);
-			HIPCHK(hipMemcpyAsync(outs[k]->obuf.p, hdr.data() + o, b, hipMemcpyHostToDevice, s));
-			outs[k]->deflate_out((int64_t)b, s, h->device);
-		}
+	open_bam(o1, out_path, h, s);
+	if (two) open_bam(o2, out2_path, h, s);
 	DevBuf<uint8_t> match, tmp; DevBuf<uint64_t> sz[2], off[2];
 	DevBuf<unsigned long long> counts; counts.alloc(2); HIPCHK(hipMemsetAsync(counts.p, 0, 2 * sizeof(unsigned long long), s));
 	StageClock ck_match(timing, s), ck_scan(timing, s), ck_gather(timing, s);
 	double ms_tiles = 0; int64_t n_tiles = 0, n_records = 0;
-	const bool lazy_keep = h->lazy_recoff; h->lazy_recoff = false;
-	struct Restore { ngsqc_handle* h; bool v; ~Restore() { h->lazy_recoff = v; } } restore{h, lazy_keep};
+	EagerRecoff eager(h);
 	stream_tiles(h, [&](const TileCtx& c) {
 		const double t0 = wall_ms();
 		const int64_t n = c.n_rec;
@@ -227,19 +185,13 @@ void extract_reads(ngsqc_handle* h, const void* names, const int32_t* name_len, 
 		const char* w = "the record sizes";
 		grow(match, (size_t)n + 1, w, T);
 		for (int k = 0; k < n_out; ++k) { grow(sz[k], (size_t)n + 1, w, T); grow(off[k], (size_t)n + 1, w, T); }
-		grow(tmp, scan_tmp_bytes(sz[0], off[0], (size_t)n, s) + 16, w, T);
+		grow(tmp, scan_tmp_bytes((size_t)n, s) + 16, w, T);
 		ck_match.mark();
 		hipLaunchKernelGGL(ex_match_kernel, dim3(grid_for(n)), dim3(256), 0, s, c.infl, rec, n, table, match.p, sz[0].p, two ? sz[1].p : nullptr, counts.p); KCHECK();
 		ck_match.mark();
 		// the position of every record in its stream, behind that stream's carried partial piece
-		uint64_t tot[2][2] = {{0, 0}, {0, 0}};
 		ck_scan.mark();
-		for (int k = 0; k < n_out; ++k)
-		{
-			size_t sb = tmp.n;
-			if (rocprim::exclusive_scan(tmp.p, sb, sz[k].p, off[k].p, (uint64_t)(outs[k]->ws + outs[k]->carry), (size_t)n, rocprim::plus<uint64_t>(), s) != hipSuccess) throw std::runtime_error("rocprim::exclusive_scan failed");
-			HIPCHK(hipMemcpyAsync(&tot[k][0], off[k].p + n - 1, 8, hipMemcpyDeviceToHost, s)); HIPCHK(hipMemcpyAsync(&tot[k][1], sz[k].p + n - 1, 8, hipMemcpyDeviceToHost, s));
-		}
+		for (int k = 0; k < n_out; ++k) outs[k]->place(tmp, sz[k].p, off[k].p, n, s);
 		ck_scan.mark();
 		HIPCHK(hipStreamSynchronize(s));
 		double dz = 0;
@@ -247,9 +199,9 @@ void extract_reads(ngsqc_handle* h, const void* names, const int32_t* name_len, 
 		{
 			BgzfStream& o = *outs[k];
 			const double dz0 = o.ms_deflate + o.ms_copy;
-			o.emit((int64_t)(tot[k][0] + tot[k][1]), s, h->device, [&](const Win& win, int64_t ws) {
+			o.emit(o.placed_end(n), s, h->device, [&](const Win& win, int64_t ws) {
 				ck_gather.mark();
-				hipLaunchKernelGGL(ex_gather_kernel, dim3(grid_for(n, 4)), dim3(256), 0, s, c.infl, rec, sz[k].p, off[k].p, n, ws, win); KCHECK();
+				launch_gather<true>(FromTile{c.infl, rec}, NoMask{}, sz[k].p, off[k].p, n, ws, win, s);
 				ck_gather.mark();
 			});
 			dz += o.ms_deflate + o.ms_copy - dz0;
@@ -260,9 +212,8 @@ void extract_reads(ngsqc_handle* h, const void* names, const int32_t* name_len, 
 	});
 	unsigned long long dc[2] = {0, 0};
 	HIPCHK(hipMemcpyAsync(dc, counts.p, sizeof(dc), hipMemcpyDeviceToHost, s)); HIPCHK(hipStreamSynchronize(s));
-	for (int k = 0; k < n_out; ++k) outs[k]->finish(s, h->device);
-	if (!o1.sink.err.empty()) throw IoError(std::string("Could not write BAM file ") + out_path + ": " + o1.sink.err);
-	if (two && !o2.sink.err.empty()) throw IoError(std::string("Could not write BAM file ") + out2_path + ": " + o2.sink.err);
+	o1.close(s, h->device, out_path);
+	if (two) o2.close(s, h->device, out2_path);
 	cnt->out = (int64_t)dc[0]; cnt->out2 = (int64_t)dc[1]; cnt->names = set.distinct;
 	if (timing)
 		fprintf(stderr, "[ngsqc] extract_reads: %.1f ms in all: name set %.1f ms (%lld names, %lld distinct, %llu slots), match and scans %.1f ms on the host's clock (by HIP events: match kernel %.1f ms, scans %.1f ms, and "
@@ -276,7 +227,7 @@ void match_names(ngsqc_handle* h, const void* names, const int32_t* name_len, in
 {
 	if (cap < 0 || (cap && !match_out)) throw ArgError("null argument");
 	check_names(names, name_len, n_names);
-	whole_file_only(h);
+	require_whole_file(h, "BamExtract");
 	const char* T = "BamExtract";
 	const uint64_t mask = name_hash_mask(h->sw.name_hash_bits);
 	hipStream_t s = h->stream;
@@ -284,19 +235,10 @@ void match_names(ngsqc_handle* h, const void* names, const int32_t* name_len, in
 	set.build(T, (const uint8_t*)names, name_len, n_names, mask, s);
 	const NameTable table = set.table(mask);
 	DevBuf<uint8_t> match;
-	int64_t done = 0;
-	const bool lazy_keep = h->lazy_recoff; h->lazy_recoff = false;
-	struct Restore { ngsqc_handle* h; bool v; ~Restore() { h->lazy_recoff = v; } } restore{h, lazy_keep};
-	stream_tiles(h, [&](const TileCtx& c) {
-		const int64_t n = c.n_rec;
-		if (n == 0) return true;
-		if (done + n > cap) throw ArgError("the match buffer is smaller than the number of records");
-		const int64_t* rec = ensure_recoff(h);
+	for_each_tile_bytes(h, match_out, cap, "the match buffer is smaller than the number of records", [&](const TileCtx& c, const int64_t* rec, int64_t n) {
 		grow(match, (size_t)n + 1, "the match bytes", T);
 		hipLaunchKernelGGL(ex_match_kernel, dim3(grid_for(n)), dim3(256), 0, s, c.infl, rec, n, table, match.p, (uint64_t*)nullptr, (uint64_t*)nullptr, (unsigned long long*)nullptr); KCHECK();
-		HIPCHK(hipMemcpyAsync(match_out + done, match.p, (size_t)n, hipMemcpyDeviceToHost, s)); HIPCHK(hipStreamSynchronize(s));
-		done += n;
-		return true;
+		return match.p;
 	});
 }
 } // namespace lib

@@ -280,8 +280,7 @@ void bam_to_fastq(ngsqc_handle* h, const ngsqc_fastq_params* fp, const char* out
 	int set_cur = 0; int64_t S = 0; uint64_t arena_used = 0;
 	int64_t max_cached = 0;
 	double ms_join = 0, t_w = wall_ms();
-	const bool lazy_keep = h->lazy_recoff; h->lazy_recoff = false;
-	struct Restore { ngsqc_handle* h; bool v; ~Restore() { h->lazy_recoff = v; } } restore{h, lazy_keep};
+	EagerRecoff eager(h);
 	stream_tiles(h, [&](const TileCtx& c) {
 		const double t0 = wall_ms();
 		const int64_t n = c.n_rec, H = j.H, N = H + n;
@@ -296,7 +295,7 @@ void bam_to_fastq(ngsqc_handle* h, const ngsqc_fastq_params* fp, const char* out
 		// (every temporary size first: a buffer must not be replaced while a queued kernel still uses it)
 		size_t tb = 0;
 		tb = std::max(tb, temp_bytes([&](size_t& b) { return rocprim::radix_sort_pairs(nullptr, b, fkey.p, sfkey.p, fidx.p, sfidx.p, (size_t)n, 0, 64, s); }));
-		tb = std::max(tb, temp_bytes([&](size_t& b) { return rocprim::exclusive_scan(nullptr, b, sz1.p, off1.p, (uint64_t)0, (size_t)n, rocprim::plus<uint64_t>(), s); }));
+		tb = std::max(tb, scan_tmp_bytes((size_t)n, s));
 		tb = std::max(tb, temp_bytes([&](size_t& b) { return rocprim::inclusive_scan(nullptr, b, dc.p, dsum.p, (size_t)n, rocprim::plus<int64_t>(), s); }));
 		tb = std::max(tb, temp_bytes([&](size_t& b) { return rocprim::reduce(nullptr, b, dsum.p, dmax.p, (int64_t)0, (size_t)n, rocprim::maximum<int64_t>(), s); }));
 		grow(tmp, tb + 16, w, T);
@@ -307,8 +306,7 @@ void bam_to_fastq(ngsqc_handle* h, const ngsqc_fastq_params* fp, const char* out
 			size_t b = tmp.n;
 			if (rocprim::radix_sort_pairs(tmp.p, b, fkey.p, sfkey.p, fidx.p, sfidx.p, (size_t)n, 0, 64, s) != hipSuccess) throw std::runtime_error("rocprim::radix_sort_pairs failed");
 			hipLaunchKernelGGL(fq_fix_kernel, dim3(grid_for(n)), dim3(256), 0, s, sfkey.p, sfidx.p, n, H, j.src.p, set_k[set_cur].p, set_v[set_cur].p, S, arena.p, cand.p, wn.p, counts.p); KCHECK();
-			b = tmp.n;
-			if (rocprim::exclusive_scan(tmp.p, b, wn.p, wo.p, (uint64_t)0, (size_t)n, rocprim::plus<uint64_t>(), s) != hipSuccess) throw std::runtime_error("rocprim::exclusive_scan failed");
+			scan_u64(tmp, wn.p, wo.p, 0, (size_t)n, s);
 			uint64_t last[2] = {0, 0};
 			HIPCHK(hipMemcpyAsync(&last[0], wo.p + n - 1, 8, hipMemcpyDeviceToHost, s)); HIPCHK(hipMemcpyAsync(&last[1], wn.p + n - 1, 8, hipMemcpyDeviceToHost, s));
 			HIPCHK(hipStreamSynchronize(s));
@@ -339,7 +337,7 @@ void bam_to_fastq(ngsqc_handle* h, const ngsqc_fastq_params* fp, const char* out
 			}
 		}
 		hipLaunchKernelGGL(fq_join_keys_kernel, dim3(grid_for(n)), dim3(256), 0, s, cand.p, fkey.p, n, H, paired ? 1 : 0, j.src.p, j.info.p, j.key.p, rp1.p, sz1.p, err.p, counts.p); KCHECK();
-		uint64_t tot1[2] = {0, 0}, tot2[2] = {0, 0}; int64_t mx = 0; unsigned long long e_ord = ~0ull;
+		int64_t mx = 0; unsigned long long e_ord = ~0ull;
 		if (paired)
 		{
 			j.sort_resolve(n, s);
@@ -349,13 +347,9 @@ void bam_to_fastq(ngsqc_handle* h, const ngsqc_fastq_params* fp, const char* out
 			b = tmp.n;
 			if (rocprim::reduce(tmp.p, b, dsum.p, dmax.p, (int64_t)0, (size_t)n, rocprim::maximum<int64_t>(), s) != hipSuccess) throw std::runtime_error("rocprim::reduce failed");
 			HIPCHK(hipMemcpyAsync(&mx, dmax.p, 8, hipMemcpyDeviceToHost, s));
-			b = tmp.n;
-			if (rocprim::exclusive_scan(tmp.p, b, sz2.p, off2.p, (uint64_t)(o2.ws + o2.carry), (size_t)n, rocprim::plus<uint64_t>(), s) != hipSuccess) throw std::runtime_error("rocprim::exclusive_scan failed");
-			HIPCHK(hipMemcpyAsync(&tot2[0], off2.p + n - 1, 8, hipMemcpyDeviceToHost, s)); HIPCHK(hipMemcpyAsync(&tot2[1], sz2.p + n - 1, 8, hipMemcpyDeviceToHost, s));
+			o2.place(tmp, sz2.p, off2.p, n, s);
 		}
-		size_t b = tmp.n;
-		if (rocprim::exclusive_scan(tmp.p, b, sz1.p, off1.p, (uint64_t)(o1.ws + o1.carry), (size_t)n, rocprim::plus<uint64_t>(), s) != hipSuccess) throw std::runtime_error("rocprim::exclusive_scan failed");
-		HIPCHK(hipMemcpyAsync(&tot1[0], off1.p + n - 1, 8, hipMemcpyDeviceToHost, s)); HIPCHK(hipMemcpyAsync(&tot1[1], sz1.p + n - 1, 8, hipMemcpyDeviceToHost, s));
+		o1.place(tmp, sz1.p, off1.p, n, s);
 		HIPCHK(hipMemcpyAsync(&e_ord, err.p, 8, hipMemcpyDeviceToHost, s));
 		if (paired) j.keep_open(n, s);   // (waits for the stream)
 		HIPCHK(hipStreamSynchronize(s));
@@ -372,11 +366,11 @@ void bam_to_fastq(ngsqc_handle* h, const ngsqc_fastq_params* fp, const char* out
 		if (paired) max_cached = std::max<int64_t>(max_cached, H + mx);
 		// the tile's entries in windows of each stream
 		const double dz0 = o1.ms_deflate + o1.ms_copy + o2.ms_deflate + o2.ms_copy;
-		o1.emit((int64_t)(tot1[0] + tot1[1]), s, h->device, [&](const Win& win, int64_t ws) {
+		o1.emit(o1.placed_end(n), s, h->device, [&](const Win& win, int64_t ws) {
 			hipLaunchKernelGGL(fq_format_kernel, dim3(grid_for(n, 4)), dim3(256), 0, s, rp1.p, sz1.p, off1.p, n, p.extend, ws, win); KCHECK();
 		});
 		if (paired)
-			o2.emit((int64_t)(tot2[0] + tot2[1]), s, h->device, [&](const Win& win, int64_t ws) {
+			o2.emit(o2.placed_end(n), s, h->device, [&](const Win& win, int64_t ws) {
 				hipLaunchKernelGGL(fq_format_kernel, dim3(grid_for(n, 4)), dim3(256), 0, s, rp2.p, sz2.p, off2.p, n, p.extend, ws, win); KCHECK();
 			});
 		HIPCHK(hipStreamSynchronize(s));   // (the old pool and the tile's bytes are no longer read)

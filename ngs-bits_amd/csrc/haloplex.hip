@@ -9,12 +9,12 @@
 //   2. long CIGARs: one wave per listed record, the lanes stride the operations, wave_sum adds up; lane 0 stores the verdict and counts a failed record. The
 //      number of listed records comes to the host with the scan's totals (one wait for both); with an empty list the kernel is not launched.
 //   3. an exclusive scan of the sizes (rocPRIM) from the stream position behind the carried partial piece.
-//   4. gather: one wave per record through recwrite.h's write_record, with 0x104 as its flag mask for a failed record. The gather runs once per output window,
+//   4. gather: one wave per record (recwrite.h's gather_kernel and write_record), with 0x104 as its flag mask for a failed record. The gather runs once per output window,
 //      so it counts nothing. Nothing else of a record changes: bin, the mate fields and the tags are the input's.
 // The reference counts reads in `int`; the counts here are 64-bit, and so is the sum of a CIGAR (2^29 operations of up to 2^28 - 1 fit).
 //
 // Compiled for gfx950 (-Rpass-analysis=kernel-resource-usage): hx_verdict_kernel 32 VGPRs, 92 SGPRs, 8 waves per SIMD; hx_long_kernel 30 VGPRs,
-// 85 SGPRs, 8 waves per SIMD; hx_gather_kernel (write_record with its CG branch inlined) 44 VGPRs, 102 SGPRs, 7 waves per SIMD. No scratch and no LDS in any of them.
+// 85 SGPRs, 8 waves per SIMD. No scratch and no LDS in either; the gather's numbers are in recwrite.h.
 #include "recwrite.h"
 #include "haloplex_visit.h"
 
@@ -83,26 +83,10 @@ __global__ __launch_bounds__(256) void hx_long_kernel(const uint8_t* __restrict_
 	}
 }
 
-// the tile's records into the window. off: absolute stream position of every record; ws: the stream position of obuf[0]
-__global__ __launch_bounds__(256) void hx_gather_kernel(const uint8_t* __restrict__ infl, const int64_t* __restrict__ recoff, const uint8_t* __restrict__ vd, const uint64_t* __restrict__ sz,
-                                                        const uint64_t* __restrict__ off, int64_t n, int64_t ws, Win w)
-{
-	const int lane = threadIdx.x & 63;
-	const int64_t nw = ((int64_t)gridDim.x * blockDim.x) >> 6;
-	for (int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6; i < n; i += nw)
-	{
-		const int64_t pos = (int64_t)off[i] - ws;
-		if (pos >= w.hi || pos + (int64_t)sz[i] <= w.lo) continue;
-		write_record(infl + recoff[i], w, pos, lane, hx_flag_mask(vd[i]));
-	}
-}
+// the gather's flag mask (recwrite.h's gather_kernel): 0x104 for a failed record
+struct HxMask { const uint8_t* vd; __device__ uint32_t operator()(int64_t i) const { return hx_flag_mask(vd[i]); } };
 
 const char* const TOOL = "BamCleanHaloplex";
-
-void whole_file_only(const ngsqc_handle* h)
-{
-	if (h->selection || h->n_shards != 1 || h->shard_own_members >= 0) throw ArgError("BamCleanHaloplex needs a handle on the whole file (not a shard, a range or regions)");
-}
 
 // the verdicts of a tile: the lane-per-record kernel; then, once the host knows how many records were listed, the wave-per-record kernel
 struct Verdicts
@@ -132,32 +116,18 @@ namespace lib {
 void clean_haloplex(ngsqc_handle* h, int32_t min_match, const char* out_path, ngsqc_haloplex_counts* cnt)
 {
 	if (!out_path || !cnt) throw ArgError("null argument");
-	whole_file_only(h);
+	require_whole_file(h, TOOL);
 	const bool timing = h->sw.timing;
 	hipStream_t s = h->stream;
 	const double t_w = wall_ms();
-	// the header: the input's bytes (magic, l_text, text, n_ref, refs), in members of its own
-	std::vector<uint8_t> hdr;
-	auto put32 = [&](uint32_t v) { for (int i = 0; i < 4; ++i) hdr.push_back((uint8_t)(v >> (8 * i))); };
-	hdr.insert(hdr.end(), {'B', 'A', 'M', 1}); put32((uint32_t)h->header_text.size()); hdr.insert(hdr.end(), h->header_text.begin(), h->header_text.end());
-	put32((uint32_t)h->ref_names.size());
-	for (size_t i = 0; i < h->ref_names.size(); ++i) { put32((uint32_t)h->ref_names[i].size() + 1); hdr.insert(hdr.end(), h->ref_names[i].begin(), h->ref_names[i].end()); hdr.push_back(0); put32((uint32_t)h->ref_lens[i]); }
 	const int64_t W = write_window_bytes(h->sw.write_window_pieces);
 	BgzfStream out(TOOL, W, -1);
-	out.sink.open(out_path, std::string("Could not open BAM/CRAM file for writing: ") + out_path);
-	for (size_t o = 0; o < hdr.size(); o += (size_t)W)   // (the header's pieces are cut from its own start: windows are whole pieces)
-	{
-		const size_t b = std::min(hdr.size() - o, (size_t)W);
-		out.ensure_obuf((int64_t)b, s);
-		HIPCHK(hipMemcpyAsync(out.obuf.p, hdr.data() + o, b, hipMemcpyHostToDevice, s));
-		out.deflate_out((int64_t)b, s, h->device);
-	}
+	open_bam(out, out_path, h, s);
 	Verdicts vb; DevBuf<uint8_t> tmp; DevBuf<uint64_t> sz, off;
 	DevBuf<unsigned long long> counts; counts.alloc(C_N); HIPCHK(hipMemsetAsync(counts.p, 0, C_N * sizeof(unsigned long long), s));
 	StageClock ck_verdict(timing, s), ck_long(timing, s), ck_scan(timing, s), ck_gather(timing, s);
 	double ms_tiles = 0; int64_t n_tiles = 0, n_records = 0, n_listed = 0;
-	const bool lazy_keep = h->lazy_recoff; h->lazy_recoff = false;
-	struct Restore { ngsqc_handle* h; bool v; ~Restore() { h->lazy_recoff = v; } } restore{h, lazy_keep};
+	EagerRecoff eager(h);
 	stream_tiles(h, [&](const TileCtx& c) {
 		const double t0 = wall_ms();
 		const int64_t n = c.n_rec;
@@ -165,18 +135,13 @@ void clean_haloplex(ngsqc_handle* h, int32_t min_match, const char* out_path, ng
 		const int64_t* rec = ensure_recoff(h);
 		const char* w = "the record sizes";
 		grow(sz, (size_t)n + 1, w, TOOL); grow(off, (size_t)n + 1, w, TOOL);
-		size_t sb = 0;
-		(void)rocprim::exclusive_scan(nullptr, sb, sz.p, off.p, (uint64_t)0, (size_t)n, rocprim::plus<uint64_t>(), s);
-		grow(tmp, sb + 16, w, TOOL);
+		grow(tmp, scan_tmp_bytes((size_t)n, s) + 16, w, TOOL);
 		ck_verdict.mark();
 		vb.begin(c.infl, rec, n, min_match, sz.p, counts.p, s);
 		ck_verdict.mark();
 		// the position of every record in the stream, behind the carried partial piece
-		uint64_t tot[2] = {0, 0};
 		ck_scan.mark();
-		sb = tmp.n;
-		if (rocprim::exclusive_scan(tmp.p, sb, sz.p, off.p, (uint64_t)(out.ws + out.carry), (size_t)n, rocprim::plus<uint64_t>(), s) != hipSuccess) throw std::runtime_error("rocprim::exclusive_scan failed");
-		HIPCHK(hipMemcpyAsync(&tot[0], off.p + n - 1, 8, hipMemcpyDeviceToHost, s)); HIPCHK(hipMemcpyAsync(&tot[1], sz.p + n - 1, 8, hipMemcpyDeviceToHost, s));
+		out.place(tmp, sz.p, off.p, n, s);
 		ck_scan.mark();
 		vb.fetch(s);
 		HIPCHK(hipStreamSynchronize(s));   // (the totals and the number of listed records are on the host)
@@ -185,9 +150,9 @@ void clean_haloplex(ngsqc_handle* h, int32_t min_match, const char* out_path, ng
 		ck_long.mark();
 		n_listed += (int64_t)vb.n_long;
 		const double dz0 = out.ms_deflate + out.ms_copy;
-		out.emit((int64_t)(tot[0] + tot[1]), s, h->device, [&](const Win& win, int64_t ws) {
+		out.emit(out.placed_end(n), s, h->device, [&](const Win& win, int64_t ws) {
 			ck_gather.mark();
-			hipLaunchKernelGGL(hx_gather_kernel, dim3(grid_for(n, 4)), dim3(256), 0, s, c.infl, rec, vb.vd.p, sz.p, off.p, n, ws, win); KCHECK();
+			launch_gather<false>(FromTile{c.infl, rec}, HxMask{vb.vd.p}, sz.p, off.p, n, ws, win, s);
 			ck_gather.mark();
 		});
 		HIPCHK(hipStreamSynchronize(s));   // (the tile's bytes are no longer read)
@@ -196,8 +161,7 @@ void clean_haloplex(ngsqc_handle* h, int32_t min_match, const char* out_path, ng
 	});
 	unsigned long long dc[C_N] = {0, 0, 0};
 	HIPCHK(hipMemcpyAsync(dc, counts.p, sizeof(dc), hipMemcpyDeviceToHost, s)); HIPCHK(hipStreamSynchronize(s));
-	out.finish(s, h->device);
-	if (!out.sink.err.empty()) throw IoError(std::string("Could not write BAM file ") + out_path + ": " + out.sink.err);
+	out.close(s, h->device, out_path);
 	cnt->reads = (int64_t)dc[C_READS]; cnt->candidates = (int64_t)dc[C_CANDIDATES]; cnt->failed = (int64_t)dc[C_FAILED];
 	if (timing)
 		fprintf(stderr, "[ngsqc] clean_haloplex: %.1f ms in all: verdicts and scan %.1f ms on the host's clock (by HIP events: verdict kernel %.1f ms, long-CIGAR kernel %.1f ms for %lld listed records, scan %.1f ms, and "
@@ -210,23 +174,14 @@ void clean_haloplex(ngsqc_handle* h, int32_t min_match, const char* out_path, ng
 void haloplex_verdicts(ngsqc_handle* h, int32_t min_match, uint8_t* out, int64_t cap)
 {
 	if (cap < 0 || (cap && !out)) throw ArgError("null argument");
-	whole_file_only(h);
+	require_whole_file(h, TOOL);
 	hipStream_t s = h->stream;
 	Verdicts vb;
-	int64_t done = 0;
-	const bool lazy_keep = h->lazy_recoff; h->lazy_recoff = false;
-	struct Restore { ngsqc_handle* h; bool v; ~Restore() { h->lazy_recoff = v; } } restore{h, lazy_keep};
-	stream_tiles(h, [&](const TileCtx& c) {
-		const int64_t n = c.n_rec;
-		if (n == 0) return true;
-		if (done + n > cap) throw ArgError("the verdict buffer is smaller than the number of records");
-		const int64_t* rec = ensure_recoff(h);
+	for_each_tile_bytes(h, out, cap, "the verdict buffer is smaller than the number of records", [&](const TileCtx& c, const int64_t* rec, int64_t n) {
 		vb.begin(c.infl, rec, n, min_match, nullptr, nullptr, s);
 		vb.fetch(s); HIPCHK(hipStreamSynchronize(s));
 		vb.finish(c.infl, rec, n, min_match, nullptr, s);
-		HIPCHK(hipMemcpyAsync(out + done, vb.vd.p, (size_t)n, hipMemcpyDeviceToHost, s)); HIPCHK(hipStreamSynchronize(s));
-		done += n;
-		return true;
+		return vb.vd.p;
 	});
 }
 } // namespace lib

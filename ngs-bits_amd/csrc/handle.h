@@ -277,6 +277,21 @@ template <typename F> int guarded(ngsqc_handle* h, F f)
 	catch (std::exception& e) { h->err = e.what(); return NGSQC_E_DEVICE; }
 }
 
+// the tools that rewrite a file see every record of it once, in file order
+inline void require_whole_file(const ngsqc_handle* h, const char* tool)
+{
+	if (h->selection || h->n_shards != 1 || h->shard_own_members >= 0) throw ArgError(std::string(tool) + " needs a handle on the whole file (not a shard, a range or regions)");
+}
+
+// a job whose every tile reads the record offsets: they are expanded with the tile (lazy_recoff off) for as long as the guard lives
+struct EagerRecoff
+{
+	ngsqc_handle* h; const bool keep;
+	explicit EagerRecoff(ngsqc_handle* hd) : h(hd), keep(hd->lazy_recoff) { h->lazy_recoff = false; }
+	~EagerRecoff() { h->lazy_recoff = keep; }
+	EagerRecoff(const EagerRecoff&) = delete; EagerRecoff& operator=(const EagerRecoff&) = delete;
+};
+
 // ---- image.hip: the BGZF member table, the BAM header, the compressed image on its way to the device, the layout of the tile stream, open ----
 void walk_bgzf(const uint8_t* file, size_t n, size_t& off, size_t off_end, int64_t max_members, uint64_t& upos, std::vector<BlockDesc>& blocks, std::vector<uint32_t>& crc, std::vector<uint64_t>* file_off = nullptr);
 void scan_bgzf(const uint8_t* file, size_t n, std::vector<BlockDesc>& blocks, std::vector<uint32_t>& crc, int64_t& total, std::vector<uint64_t>* file_off, int threads, bool* in_pieces = nullptr);

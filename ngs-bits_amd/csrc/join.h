@@ -1,5 +1,6 @@
-// The mate join by read name and the windowed BGZF writer, shared by the tools that pair records and write compressed output (BamFilter: pairs.hip,
-// BamToFastq: fastq.hip, BamDownsample: downsample.hip). One pass over the tiles; per tile (NameJoin):
+// The mate join by read name and the windowed BGZF writer, shared by the tools that pair records and / or write compressed output (NameJoin: BamFilter pairs.hip,
+// BamToFastq fastq.hip, BamDownsample downsample.hip, BamRemoveVariants rmvar.hip, BamClipOverlap clip.hip; BgzfStream: those and BamExtract extract.hip,
+// BamCleanHaloplex haloplex.hip). One pass over the tiles; per tile (NameJoin):
 //   1. the tool's keys kernel gives every tile record a 64-bit name hash (KEY_NONE: the record takes no part), its source pointer and a 32-bit info word whose
 //      bit 31 says the record is kept ("passes"); val[e] = e for every entry.
 //   2. sort: the open entries carried over from earlier tiles ("held", in (hash, ordinal) order) followed by the tile's records, radix-sorted by hash (rocPRIM,
@@ -9,7 +10,10 @@
 //      pairs kept / not kept.
 //   4. held: the entries still open are compacted; their bytes are copied out of the tile buffer (the whole record if it passes, the name alone if not).
 // BgzfStream cuts one output stream into windows of whole 0xff00-byte pieces: the tool fills a window, its whole pieces go through the encoder (deflate.hip)
-// and a host thread writes the members while the next window is filled; the partial piece moves to the front.
+// and a host thread writes the members while the next window is filled; the partial piece moves to the front. Around emit it holds what every writer does
+// the same way: put_host (a header in members of its own), place / placed_end (the stream positions of a tile's items and where they end) and close (finish,
+// and the error of a failed BAM write); the BAM writers (recwrite.h's open_bam) use all of them, BamToFastq place.
+// scan_u64 / scan_tmp_bytes: the one checked rocPRIM exclusive sum of the join, of place and of the tools' own scans.
 #pragma once
 #include "handle.h"
 #include "rec.h"
@@ -170,7 +174,6 @@ struct FileSink
 const uint8_t BGZF_EOF[28] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 0x42, 0x43, 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 
 // device buffers of the join and the held set grow with the tile and with the names still open: planned against hipMemGetInfo before they are allocated
-// device buffers of the join and the held set grow with the tile and with the names still open: planned against hipMemGetInfo before they are allocated
 template <typename T> void grow(DevBuf<T>& b, size_t n, const char* what, const char* tool)
 {
 	if (b.n >= n) return;
@@ -184,6 +187,19 @@ template <typename T> void grow(DevBuf<T>& b, size_t n, const char* what, const 
 	}
 	try { b.alloc(n + n / 4 + 1024); }
 	catch (std::exception& e) { throw std::runtime_error(std::string(tool) + ": " + what + " does not fit in device memory (" + std::to_string((n * sizeof(T)) >> 20) + " MiB asked for; " + e.what() + ")"); }
+}
+
+// the checked exclusive sum into uint64 positions (rocPRIM), and the temporary bytes it asks for: tmp holds at least scan_tmp_bytes<In>(n, s) bytes
+template <typename In = uint64_t> size_t scan_tmp_bytes(size_t n, hipStream_t s)
+{
+	size_t sb = 0;
+	(void)rocprim::exclusive_scan(nullptr, sb, (const In*)nullptr, (uint64_t*)nullptr, (uint64_t)0, n, rocprim::plus<uint64_t>(), s);
+	return sb;
+}
+template <typename In> void scan_u64(DevBuf<uint8_t>& tmp, const In* in, uint64_t* out, uint64_t init, size_t n, hipStream_t s)
+{
+	size_t sb = tmp.n;
+	if (rocprim::exclusive_scan(tmp.p, sb, in, out, init, n, rocprim::plus<uint64_t>(), s) != hipSuccess) throw std::runtime_error("rocprim::exclusive_scan failed");
 }
 
 // A window of an output stream: the bytes [lo, hi) of obuf are written, a record at position pos (relative to obuf[0]; negative: it began in an earlier window)
@@ -212,11 +228,9 @@ struct NameJoin
 		}
 		if (!N) return;
 		// (every temporary size first: a buffer must not be replaced while a queued kernel still uses it)
-		size_t tb = 0, sb1 = 0, sb2 = 0;
+		size_t tb = 0;
 		(void)rocprim::radix_sort_pairs(nullptr, tb, key.p, skey.p, val.p, sval.p, N, 0, 64, s);
-		(void)rocprim::exclusive_scan(nullptr, sb1, nb.p, boff.p, (uint64_t)0, N, rocprim::plus<uint64_t>(), s);
-		(void)rocprim::exclusive_scan(nullptr, sb2, held.p, hpos.p, (uint64_t)0, N, rocprim::plus<uint64_t>(), s);
-		grow(tmp, std::max(tb, std::max(sb1, sb2)) + 16, w, tool);
+		grow(tmp, std::max(tb, std::max(scan_tmp_bytes(N, s), scan_tmp_bytes<uint8_t>(N, s))) + 16, w, tool);
 	}
 	// after the tool's keys kernel: sort by hash and pair
 	void sort_resolve(int64_t n, hipStream_t s)
@@ -234,10 +248,8 @@ struct NameJoin
 		const int64_t N = H + n;
 		hipLaunchKernelGGL(held_bytes_kernel, dim3(grid_for(N)), dim3(256), 0, s, held.p, sval.p, N, src.p, info.p, nb.p); KCHECK();
 		uint64_t hcnt[4] = {0, 0, 0, 0};
-		size_t sb = tmp.n;
-		if (rocprim::exclusive_scan(tmp.p, sb, nb.p, boff.p, (uint64_t)0, (size_t)N, rocprim::plus<uint64_t>(), s) != hipSuccess) throw std::runtime_error("rocprim::exclusive_scan failed");
-		sb = tmp.n;
-		if (rocprim::exclusive_scan(tmp.p, sb, held.p, hpos.p, (uint64_t)0, (size_t)N, rocprim::plus<uint64_t>(), s) != hipSuccess) throw std::runtime_error("rocprim::exclusive_scan failed");
+		scan_u64(tmp, nb.p, boff.p, 0, (size_t)N, s);
+		scan_u64(tmp, held.p, hpos.p, 0, (size_t)N, s);
 		HIPCHK(hipMemcpyAsync(&hcnt[0], boff.p + N - 1, 8, hipMemcpyDeviceToHost, s)); HIPCHK(hipMemcpyAsync(&hcnt[1], nb.p + N - 1, 8, hipMemcpyDeviceToHost, s));
 		HIPCHK(hipMemcpyAsync(&hcnt[2], hpos.p + N - 1, 8, hipMemcpyDeviceToHost, s));
 		uint8_t last_held = 0; HIPCHK(hipMemcpyAsync(&last_held, held.p + N - 1, 1, hipMemcpyDeviceToHost, s));
@@ -281,6 +293,7 @@ struct BgzfStream
 	DevBuf<uint8_t> obuf, zbuf;
 	int64_t carry = 0, ws = 0;   // ws: stream position of obuf[0]; obuf[0, carry) holds the partial piece in front of what comes next
 	double ms_deflate = 0, ms_copy = 0;
+	uint64_t tot[2] = {0, 0};   // place(): the last placed record's position and size, on the host behind the caller's next wait for the stream
 	BgzfStream(const char* t, int64_t w, int lv) : tool(t), W(w), level(lv) {}
 	void deflate_out(int64_t bytes, hipStream_t s, int device)   // the first `bytes` of obuf (whole pieces, or the tail at the end) to the file
 	{
@@ -325,7 +338,32 @@ struct BgzfStream
 			if (w_end >= out_end) break;
 		}
 	}
+	// host bytes in front of the stream, in members of their own (a BAM header): pieces cut from the buffer's own start, at most W bytes per step, as windows
+	// are whole pieces; the stream positions start behind them at 0
+	void put_host(const uint8_t* p, size_t n, hipStream_t s, int device)
+	{
+		for (size_t o = 0; o < n; o += (size_t)W)
+		{
+			const size_t k = std::min(n - o, (size_t)W);
+			ensure_obuf((int64_t)k, s);
+			HIPCHK(hipMemcpyAsync(obuf.p, p + o, k, hipMemcpyHostToDevice, s));
+			deflate_out((int64_t)k, s, device);
+		}
+	}
+	// the stream positions off[0, n) of n > 0 items of sz[] bytes, behind the carried partial piece; the totals are queued for placed_end
+	void place(DevBuf<uint8_t>& tmp, const uint64_t* sz, uint64_t* off, int64_t n, hipStream_t s)
+	{
+		scan_u64(tmp, sz, off, (uint64_t)(ws + carry), (size_t)n, s);
+		HIPCHK(hipMemcpyAsync(&tot[0], off + n - 1, 8, hipMemcpyDeviceToHost, s)); HIPCHK(hipMemcpyAsync(&tot[1], sz + n - 1, 8, hipMemcpyDeviceToHost, s));
+	}
+	// the stream position behind what place() placed (after the caller's wait for the stream); n == 0: nothing was placed
+	int64_t placed_end(int64_t n) const { return n ? (int64_t)(tot[0] + tot[1]) : ws + carry; }
 	void finish(hipStream_t s, int device) { deflate_out(carry, s, device); carry = 0; sink.put_host(BGZF_EOF, sizeof(BGZF_EOF)); sink.finish(); }
+	void close(hipStream_t s, int device, const char* path)   // finish, for a BAM: a failed write is the caller's error
+	{
+		finish(s, device);
+		if (!sink.err.empty()) throw IoError(std::string("Could not write BAM file ") + path + ": " + sink.err);
+	}
 };
 } // namespace
 } // namespace ngsqc

@@ -85,31 +85,17 @@ namespace lib {
 void filter_pairs(ngsqc_handle* h, const ngsqc_pair_filter* fp, const char* out_path, int64_t* passed, int64_t* dropped)
 {
 	if (!fp || !out_path || !passed || !dropped) throw ArgError("null argument");
-	if (h->selection || h->n_shards != 1 || h->shard_own_members >= 0) throw ArgError("BamFilter needs a handle on the whole file (not a shard, a range or regions)");
+	require_whole_file(h, "BamFilter");
 	PairParams p{fp->min_mq, fp->max_mq, fp->max_mm, fp->max_gap, fp->min_dup, fp->max_is, name_hash_mask(h->sw.name_hash_bits)};
 	const bool timing = h->sw.timing;
 	hipStream_t s = h->stream;
-	// the header: the input's bytes (magic, l_text, text, n_ref, refs), in members of its own
-	std::vector<uint8_t> hdr;
-	auto put32 = [&](uint32_t v) { for (int i = 0; i < 4; ++i) hdr.push_back((uint8_t)(v >> (8 * i))); };
-	hdr.insert(hdr.end(), {'B', 'A', 'M', 1}); put32((uint32_t)h->header_text.size()); hdr.insert(hdr.end(), h->header_text.begin(), h->header_text.end());
-	put32((uint32_t)h->ref_names.size());
-	for (size_t i = 0; i < h->ref_names.size(); ++i) { put32((uint32_t)h->ref_names[i].size() + 1); hdr.insert(hdr.end(), h->ref_names[i].begin(), h->ref_names[i].end()); hdr.push_back(0); put32((uint32_t)h->ref_lens[i]); }
 	const int64_t W = write_window_bytes(h->sw.write_window_pieces);
 	BgzfStream out("BamFilter", W, -1);
-	out.sink.open(out_path, std::string("Could not open BAM/CRAM file for writing: ") + out_path);
 	NameJoin j("BamFilter", s);
 	DevBuf<uint64_t> sz, off;
 	double ms_pair = 0, t_w = wall_ms();
-	for (size_t o = 0; o < hdr.size(); o += (size_t)W)   // (the header's pieces are cut from its own start: windows are whole pieces)
-	{
-		const size_t k = std::min(hdr.size() - o, (size_t)W);
-		out.ensure_obuf((int64_t)k, s);
-		HIPCHK(hipMemcpyAsync(out.obuf.p, hdr.data() + o, k, hipMemcpyHostToDevice, s));
-		out.deflate_out((int64_t)k, s, h->device);
-	}
-	const bool lazy_keep = h->lazy_recoff; h->lazy_recoff = false;
-	struct Restore { ngsqc_handle* h; bool v; ~Restore() { h->lazy_recoff = v; } } restore{h, lazy_keep};
+	open_bam(out, out_path, h, s);
+	EagerRecoff eager(h);
 	stream_tiles(h, [&](const TileCtx& c) {
 		const double t0 = wall_ms();
 		const int64_t n = c.n_rec, H = j.H, N = H + n;
@@ -120,19 +106,15 @@ void filter_pairs(ngsqc_handle* h, const ngsqc_pair_filter* fp, const char* out_
 		hipLaunchKernelGGL(pair_keys_kernel, dim3(grid_for(N)), dim3(256), 0, s, c.infl, rec, n, H, p, j.key.p, j.val.p, j.src.p, j.info.p); KCHECK();
 		j.sort_resolve(n, s);
 		// the output of the tile's pairs, behind the carried partial piece
-		uint64_t tot[2] = {0, 0};
 		if (n)
 		{
 			hipLaunchKernelGGL(pair_sizes_kernel, dim3(grid_for(n)), dim3(256), 0, s, j.close_of.p, j.info.p, n, H, sz.p); KCHECK();
-			size_t sb = j.tmp.n;
-			if (rocprim::exclusive_scan(j.tmp.p, sb, sz.p, off.p, (uint64_t)(out.ws + out.carry), (size_t)n, rocprim::plus<uint64_t>(), s) != hipSuccess) throw std::runtime_error("rocprim::exclusive_scan failed");
-			HIPCHK(hipMemcpyAsync(&tot[0], off.p + n - 1, 8, hipMemcpyDeviceToHost, s)); HIPCHK(hipMemcpyAsync(&tot[1], sz.p + n - 1, 8, hipMemcpyDeviceToHost, s));
+			out.place(j.tmp, sz.p, off.p, n, s);
 		}
-		j.keep_open(n, s);   // (waits for the stream: tot is on the host)
-		const int64_t out_end = n ? (int64_t)(tot[0] + tot[1]) : out.ws + out.carry;   // (stream position)
+		j.keep_open(n, s);   // (waits for the stream: the placed end is on the host)
 		// the tile's pairs in windows of the stream
 		const double dz0 = out.ms_deflate + out.ms_copy;
-		out.emit(out_end, s, h->device, [&](const Win& w, int64_t ws) {
+		out.emit(out.placed_end(n), s, h->device, [&](const Win& w, int64_t ws) {
 			if (n) { hipLaunchKernelGGL(pair_gather_kernel, dim3(grid_for(n, 4)), dim3(256), 0, s, j.close_of.p, sz.p, off.p, n, H, j.src.p, j.info.p, ws, w); KCHECK(); }
 		});
 		HIPCHK(hipStreamSynchronize(s));   // (the old pool and the tile's bytes are no longer read)
@@ -142,8 +124,7 @@ void filter_pairs(ngsqc_handle* h, const ngsqc_pair_filter* fp, const char* out_
 	});
 	unsigned long long cnt[4] = {0, 0, 0, 0};
 	j.read_counts(cnt, s);
-	out.finish(s, h->device);
-	if (!out.sink.err.empty()) throw IoError(std::string("Could not write BAM file ") + out_path + ": " + out.sink.err);
+	out.close(s, h->device, out_path);
 	*passed = (int64_t)cnt[0]; *dropped = (int64_t)cnt[1];
 	if (timing)
 		fprintf(stderr, "[ngsqc] filter_pairs: %.1f ms in all: pair join and gather %.1f ms, deflate %.1f ms, copy to pinned memory %.1f ms, file writes %.1f ms (host thread), %lld open names at the end, windows of %lld bytes\n",

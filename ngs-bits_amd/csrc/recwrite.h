@@ -1,6 +1,15 @@
-// The bytes BamWriter::writeAlignment writes for a record (src/cppNGS/BamWriter.cpp over htslib's bam_write1), shared by the tools that gather records into a
-// BAM output stream (BamFilter: pairs.hip, BamDownsample: downsample.hip, and the writers after them): the size a record takes in the output and the wave-wide
-// copy into a window, with bits OR-ed into the copy's flag word where a tool asks for it (BamCleanHaloplex: haloplex.hip).
+// The BAM-output path of the tools that stream a BAM and write one (BamFilter: pairs.hip, BamDownsample: downsample.hip, BamExtract: extract.hip,
+// BamRemoveVariants: rmvar.hip, BamClipOverlap: clip.hip, BamCleanHaloplex: haloplex.hip), on top of join.h's BgzfStream:
+//   - the bytes BamWriter::writeAlignment writes for a record (src/cppNGS/BamWriter.cpp over htslib's bam_write1): the size a record takes in the output
+//     (out_size) and the wave-wide copy into a window (write_record), with bits OR-ed into the copy's flag word where a tool asks for it;
+//   - bam_header_bytes / open_bam: the output's sink and the input's header in front of it (all six);
+//   - gather_kernel: the records that leave as they came, a wave each. Its source is FromTile (BamExtract, BamCleanHaloplex) or FromPtrs (BamClipOverlap's open
+//     names), its flag mask NoMask or the tool's own (BamCleanHaloplex). The gathers of pairs carry tool logic and stay with their tools;
+//   - for_each_tile_bytes: the entry points that hand out one byte per record and write nothing (ngsqc_match_names, _variant_verdicts, _haloplex_verdicts);
+//   - fetch_rec_head: the start of a failing record for the reference's error message (BamRemoveVariants, BamClipOverlap).
+// Compiled for gfx950 (-Rpass-analysis=kernel-resource-usage), no scratch and no LDS: gather_kernel<true, FromTile, NoMask> 42 VGPRs, 97 SGPRs, 8 waves per
+// SIMD; <false, FromTile, HxMask> (haloplex.hip) 44 VGPRs, 102 SGPRs, 7 waves per SIMD; <false, FromPtrs, NoMask> 40 VGPRs, 92 SGPRs, 8 waves per SIMD. The mask
+// is a type, not an argument that is usually 0: the two branches of write_record's copy loop in one kernel cost the maskless gather a wave of occupancy.
 #pragma once
 #include "join.h"
 
@@ -81,6 +90,81 @@ __device__ void write_record(const uint8_t* __restrict__ s, const Win& w, int64_
 	for (const uint8_t* x = sq; x < tag0; ++x) put(w, o, *x);
 	for (const uint8_t* x = tag1; x < e; ++x) put(w, o, *x);
 	if (!inl) for (const uint8_t* x = tag0; x < tag1; ++x) put(w, o, *x);
+}
+
+// the records that leave as they came, one wave per record: src(i) is record i's first byte, mask(i) the bits OR-ed into its flag word. Sparse: some records
+// add nothing (sz 0: they belong to another stream) and are skipped before their position is read; where every record is written the test would only hold back
+// the load of off[i] (measured: 0.5 % of the kernel). A wave copies about four records, so its prologue counts: the mask comes last, which keeps the pointers in
+// one 32-byte load of the kernel arguments. off: absolute stream positions; ws: the stream position of obuf[0]
+struct FromTile { const uint8_t* __restrict__ infl; const int64_t* __restrict__ recoff; __device__ const uint8_t* operator()(int64_t i) const { return infl + recoff[i]; } };
+struct FromPtrs { const uint64_t* __restrict__ src; __device__ const uint8_t* operator()(int64_t i) const { return (const uint8_t*)(uintptr_t)src[i]; } };
+struct NoMask { __device__ uint32_t operator()(int64_t) const { return 0; } };
+template <bool Sparse, typename Src, typename Mask>
+__global__ __launch_bounds__(256) void gather_kernel(Src src, const uint64_t* __restrict__ sz, const uint64_t* __restrict__ off, int64_t n, int64_t ws, Win w, Mask mask)
+{
+	const int lane = threadIdx.x & 63;
+	const int64_t nw = ((int64_t)gridDim.x * blockDim.x) >> 6;
+	for (int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6; i < n; i += nw)
+	{
+		if (Sparse && !sz[i]) continue;
+		const int64_t pos = (int64_t)off[i] - ws;
+		if (pos >= w.hi || pos + (int64_t)sz[i] <= w.lo) continue;
+		write_record(src(i), w, pos, lane, mask(i));
+	}
+}
+template <bool Sparse, typename Src, typename Mask> void launch_gather(Src src, Mask mask, const uint64_t* sz, const uint64_t* off, int64_t n, int64_t ws, const Win& w, hipStream_t s)
+{
+	hipLaunchKernelGGL((gather_kernel<Sparse, Src, Mask>), dim3(grid_for(n, 4)), dim3(256), 0, s, src, sz, off, n, ws, w, mask); KCHECK();
+}
+
+// the header: the input's bytes (magic, l_text, text, n_ref, refs); no @PG line (BamWriter::writeHeader copies the input's)
+inline std::vector<uint8_t> bam_header_bytes(const ngsqc_handle* h)
+{
+	std::vector<uint8_t> hdr;
+	auto put32 = [&](uint32_t v) { for (int i = 0; i < 4; ++i) hdr.push_back((uint8_t)(v >> (8 * i))); };
+	hdr.insert(hdr.end(), {'B', 'A', 'M', 1}); put32((uint32_t)h->header_text.size()); hdr.insert(hdr.end(), h->header_text.begin(), h->header_text.end());
+	put32((uint32_t)h->ref_names.size());
+	for (size_t i = 0; i < h->ref_names.size(); ++i) { put32((uint32_t)h->ref_names[i].size() + 1); hdr.insert(hdr.end(), h->ref_names[i].begin(), h->ref_names[i].end()); hdr.push_back(0); put32((uint32_t)h->ref_lens[i]); }
+	return hdr;
+}
+
+// the output file and, in members of its own, the header
+inline void open_bam(BgzfStream& out, const char* path, const ngsqc_handle* h, hipStream_t s)
+{
+	out.sink.open(path, std::string("Could not open BAM/CRAM file for writing: ") + path);
+	const std::vector<uint8_t> hdr = bam_header_bytes(h);
+	out.put_host(hdr.data(), hdr.size(), s, h->device);
+}
+
+// one byte per record of the file into out[0, cap): run(c, rec, n) queues the tool's kernels for the resident tile and returns the device pointer to its n bytes.
+// Returns the number of records
+template <typename F> int64_t for_each_tile_bytes(ngsqc_handle* h, uint8_t* out, int64_t cap, const char* too_small_msg, F run)
+{
+	hipStream_t s = h->stream;
+	int64_t done = 0;
+	EagerRecoff eager(h);
+	stream_tiles(h, [&](const TileCtx& c) {
+		const int64_t n = c.n_rec;
+		if (n == 0) return true;
+		if (done + n > cap) throw ArgError(too_small_msg);
+		const uint8_t* d = run(c, ensure_recoff(h), n);
+		HIPCHK(hipMemcpyAsync(out + done, d, (size_t)n, hipMemcpyDeviceToHost, s)); HIPCHK(hipStreamSynchronize(s));
+		done += n;
+		return true;
+	});
+	return done;
+}
+
+// record i of the resident tile for an error message: its offset in the tile, its first bytes and its name. Waits for the stream (twice): what the caller
+// queued in front is on the host as well
+struct RecHead { int64_t off = 0; uint8_t head[36 + 256] = {0}; std::string name; };
+inline RecHead fetch_rec_head(const TileCtx& c, const int64_t* rec, int64_t i, hipStream_t s)
+{
+	RecHead r;
+	HIPCHK(hipMemcpyAsync(&r.off, rec + i, 8, hipMemcpyDeviceToHost, s)); HIPCHK(hipStreamSynchronize(s));
+	HIPCHK(hipMemcpyAsync(r.head, c.infl + r.off, (size_t)std::min<int64_t>((int64_t)sizeof(r.head), c.total - r.off), hipMemcpyDeviceToHost, s)); HIPCHK(hipStreamSynchronize(s));
+	r.name.assign((const char*)r.head + 36, strnlen((const char*)r.head + 36, r.head[12]));
+	return r;
 }
 } // namespace
 } // namespace ngsqc

@@ -252,11 +252,6 @@ struct RmDevTable
 	RmTable table() const { return RmTable{v.p, maxend.p, tid_first.p, n_ref}; }
 };
 
-void whole_file(const ngsqc_handle* h)
-{
-	if (h->selection || h->n_shards != 1 || h->shard_own_members >= 0) throw ArgError("BamRemoveVariants needs a handle on the whole file (not a shard, a range or regions)");
-}
-
 // the verdicts of a tile: the thread-per-record kernel, then the listed long records
 struct VerdictBufs
 {
@@ -278,21 +273,20 @@ struct VerdictBufs
 {
 	const int64_t i = ord - c.ord_base;
 	if (i < 0 || i >= c.n_rec) throw std::runtime_error("BamRemoveVariants: the failing record is not in the resident tile");
-	uint8_t vd = 0; int32_t ev = -1; int64_t ro = 0; uint8_t head[36 + 256] = {0};
+	uint8_t vd = 0; int32_t ev = -1;
 	HIPCHK(hipMemcpyAsync(&vd, vb.vd.p + i, 1, hipMemcpyDeviceToHost, s)); HIPCHK(hipMemcpyAsync(&ev, vb.ev.p + i, 4, hipMemcpyDeviceToHost, s));
-	HIPCHK(hipMemcpyAsync(&ro, rec + i, 8, hipMemcpyDeviceToHost, s)); HIPCHK(hipStreamSynchronize(s));
-	HIPCHK(hipMemcpyAsync(head, c.infl + ro, (size_t)std::min<int64_t>((int64_t)sizeof(head), c.total - ro), hipMemcpyDeviceToHost, s)); HIPCHK(hipStreamSynchronize(s));
+	const RecHead rh = fetch_rec_head(c, rec, i, s);   // (waits for the stream)
+	const uint8_t* head = rh.head; const std::string& name = rh.name;
 	const int code = vd >> 4 & 3;
 	cnt->err_record = ord; cnt->err_code = code; cnt->err_variant = code == NGSQC_RMERR_BAD_BASE ? ev : (int32_t)tab.orig[(size_t)ev];
 	int32_t pos; memcpy(&pos, head + 8, 4);
-	const std::string name((const char*)head + 36, strnlen((const char*)head + 36, head[12]));
 	if (code == NGSQC_RMERR_POS_NOT_FOUND)
 		throw FormatError("Could not find position " + std::to_string(tab.lines[(size_t)ev].start) + " in read " + name + " with start position " + std::to_string((long long)pos + 1) + "!");
 	if (code == NGSQC_RMERR_BAD_BASE)
 	{
 		// (the base itself: one more byte of the record)
 		uint32_t w2 = 0; memcpy(&w2, head + 16, 4);
-		uint8_t b = 0; HIPCHK(hipMemcpy(&b, c.infl + ro + 36 + head[12] + 4ll * (w2 & 0xffff) + (ev >> 1), 1, hipMemcpyDeviceToHost));
+		uint8_t b = 0; HIPCHK(hipMemcpy(&b, c.infl + rh.off + 36 + head[12] + 4ll * (w2 & 0xffff) + (ev >> 1), 1, hipMemcpyDeviceToHost));
 		throw FormatError(std::string("Cannot store character '") + "=ACMGRSVTWYHKDBN"[(b >> ((~ev & 1) << 2)) & 15] + "' in BAM/CRAM file. Only A,C,G,T,N are allowed!");
 	}
 	throw FormatError("BamRemoveVariants: read " + name + " visits variant line " + std::to_string(cnt->err_variant) + ", which is no valid variant");
@@ -303,8 +297,8 @@ namespace lib {
 void remove_variants(ngsqc_handle* h, const ngsqc_rm_variant* variants, int64_t n_var, const ngsqc_rm_params* p, const char* out_path, ngsqc_rm_counts* cnt)
 {
 	if (!p || !out_path || !cnt || n_var < 0 || (n_var && !variants)) throw ArgError("null argument");
-	whole_file(h);
 	const char* TOOL = "BamRemoveVariants";
+	require_whole_file(h, TOOL);
 	const RmMode m{p->mask ? 1 : 0, p->single_end ? 1 : 0, p->keep_indels ? 1 : 0};
 	const uint64_t hash_mask = name_hash_mask(h->sw.name_hash_bits);
 	const bool timing = h->sw.timing;
@@ -314,30 +308,16 @@ void remove_variants(ngsqc_handle* h, const ngsqc_rm_variant* variants, int64_t 
 	RmDevTable tab; tab.build(h, variants, n_var, s);
 	const RmTable T = tab.table();
 	const double ms_table = wall_ms() - t_w;
-	// the header: the input's bytes (magic, l_text, text, n_ref, refs), in members of its own; no @PG line (the reference's writeHeader copies the input's)
-	std::vector<uint8_t> hdr;
-	auto put32 = [&](uint32_t v) { for (int i = 0; i < 4; ++i) hdr.push_back((uint8_t)(v >> (8 * i))); };
-	hdr.insert(hdr.end(), {'B', 'A', 'M', 1}); put32((uint32_t)h->header_text.size()); hdr.insert(hdr.end(), h->header_text.begin(), h->header_text.end());
-	put32((uint32_t)h->ref_names.size());
-	for (size_t i = 0; i < h->ref_names.size(); ++i) { put32((uint32_t)h->ref_names[i].size() + 1); hdr.insert(hdr.end(), h->ref_names[i].begin(), h->ref_names[i].end()); hdr.push_back(0); put32((uint32_t)h->ref_lens[i]); }
 	const int64_t W = write_window_bytes(h->sw.write_window_pieces);
 	BgzfStream out(TOOL, W, -1);
-	out.sink.open(out_path, std::string("Could not open BAM/CRAM file for writing: ") + out_path);
 	NameJoin j(TOOL, s);
 	VerdictBufs vb;
 	DevBuf<uint64_t> sz, off; DevBuf<unsigned long long> counts; counts.alloc(C_N);
 	HIPCHK(hipMemsetAsync(counts.p, 0, C_N * sizeof(unsigned long long), s)); HIPCHK(hipMemsetAsync(counts.p + C_ERR_ORD, 0xff, sizeof(unsigned long long), s));
 	StageClock ck_verdict(timing, s), ck_gather(timing, s);
 	double ms_tiles = 0;
-	for (size_t o = 0; o < hdr.size(); o += (size_t)W)   // (the header's pieces are cut from its own start: windows are whole pieces)
-	{
-		const size_t k = std::min(hdr.size() - o, (size_t)W);
-		out.ensure_obuf((int64_t)k, s);
-		HIPCHK(hipMemcpyAsync(out.obuf.p, hdr.data() + o, k, hipMemcpyHostToDevice, s));
-		out.deflate_out((int64_t)k, s, h->device);
-	}
-	const bool lazy_keep = h->lazy_recoff; h->lazy_recoff = false;
-	struct Restore { ngsqc_handle* h; bool v; ~Restore() { h->lazy_recoff = v; } } restore{h, lazy_keep};
+	open_bam(out, out_path, h, s);
+	EagerRecoff eager(h);
 	stream_tiles(h, [&](const TileCtx& c) {
 		const double t0 = wall_ms();
 		const int64_t n = c.n_rec, H = j.H, N = H + n;   // (single-end: nothing is ever held, H stays 0)
@@ -349,22 +329,19 @@ void remove_variants(ngsqc_handle* h, const ngsqc_rm_variant* variants, int64_t 
 		vb.run(c.infl, rec, n, H, T, m, hash_mask, VerdictOut{j.key.p, j.val.p, j.src.p, j.info.p, nullptr, nullptr, counts.p}, s);
 		ck_verdict.mark();
 		if (!m.single_end) j.sort_resolve(n, s);
-		uint64_t tot[2] = {0, 0}; unsigned long long err_ord = ~0ull;
+		unsigned long long err_ord = ~0ull;
 		if (n)
 		{
 			if (m.single_end) { hipLaunchKernelGGL(rm_single_post_kernel, dim3(grid_for(n)), dim3(256), 0, s, j.info.p, vb.vd.p, n, c.ord_base, sz.p, counts.p); KCHECK(); }
 			else { hipLaunchKernelGGL(rm_pair_post_kernel, dim3(grid_for(n)), dim3(256), 0, s, j.close_of.p, j.info.p, vb.vd.p, n, H, c.ord_base, sz.p, counts.p); KCHECK(); }
-			size_t sb = j.tmp.n;
-			if (rocprim::exclusive_scan(j.tmp.p, sb, sz.p, off.p, (uint64_t)(out.ws + out.carry), (size_t)n, rocprim::plus<uint64_t>(), s) != hipSuccess) throw std::runtime_error("rocprim::exclusive_scan failed");
-			HIPCHK(hipMemcpyAsync(&tot[0], off.p + n - 1, 8, hipMemcpyDeviceToHost, s)); HIPCHK(hipMemcpyAsync(&tot[1], sz.p + n - 1, 8, hipMemcpyDeviceToHost, s));
+			out.place(j.tmp, sz.p, off.p, n, s);
 			HIPCHK(hipMemcpyAsync(&err_ord, counts.p + C_ERR_ORD, 8, hipMemcpyDeviceToHost, s));
 		}
 		if (m.single_end) HIPCHK(hipStreamSynchronize(s));
-		else j.keep_open(n, s);   // (waits for the stream: tot and err_ord are on the host)
+		else j.keep_open(n, s);   // (waits for the stream: the placed end and err_ord are on the host)
 		if (err_ord != ~0ull) throw_record_error(c, rec, (int64_t)err_ord, vb, tab, cnt, s);
-		const int64_t out_end = n ? (int64_t)(tot[0] + tot[1]) : out.ws + out.carry;   // (stream position)
 		const double dz0 = out.ms_deflate + out.ms_copy;
-		out.emit(out_end, s, h->device, [&](const Win& w, int64_t ws) {
+		out.emit(out.placed_end(n), s, h->device, [&](const Win& w, int64_t ws) {
 			if (!n) return;
 			ck_gather.mark();
 			if (m.single_end) hipLaunchKernelGGL(rm_single_gather_kernel, dim3(grid_for(n, 4)), dim3(256), 0, s, sz.p, off.p, n, j.src.p, j.info.p, ws, w, T, m);
@@ -380,8 +357,7 @@ void remove_variants(ngsqc_handle* h, const ngsqc_rm_variant* variants, int64_t 
 	unsigned long long jc[4] = {0, 0, 0, 0}, dc[C_N];
 	j.read_counts(jc, s);
 	HIPCHK(hipMemcpyAsync(dc, counts.p, sizeof(dc), hipMemcpyDeviceToHost, s)); HIPCHK(hipStreamSynchronize(s));
-	out.finish(s, h->device);
-	if (!out.sink.err.empty()) throw IoError(std::string("Could not write BAM file ") + out_path + ": " + out.sink.err);
+	out.close(s, h->device, out_path);
 	cnt->passed = (int64_t)(m.single_end ? dc[C_SE_PASSED] : jc[0]); cnt->dropped = (int64_t)(m.single_end ? dc[C_SE_DROPPED] : jc[1]);
 	cnt->modified = (int64_t)dc[C_MODIFIED] - (int64_t)dc[C_MOD_MINUS]; cnt->skipped = (int64_t)dc[C_SKIPPED];
 	if (timing)
@@ -395,26 +371,17 @@ void remove_variants(ngsqc_handle* h, const ngsqc_rm_variant* variants, int64_t 
 void variant_verdicts(ngsqc_handle* h, const ngsqc_rm_variant* variants, int64_t n_var, const ngsqc_rm_params* p, uint8_t* out, int64_t cap)
 {
 	if (!p || n_var < 0 || (n_var && !variants) || cap < 0 || (cap && !out)) throw ArgError("null argument");
-	whole_file(h);
+	require_whole_file(h, "BamRemoveVariants");
 	const RmMode m{p->mask ? 1 : 0, p->single_end ? 1 : 0, p->keep_indels ? 1 : 0};
 	hipStream_t s = h->stream;
 	RmDevTable tab; tab.build(h, variants, n_var, s);
 	const RmTable T = tab.table();
 	VerdictBufs vb;
-	int64_t done = 0;
-	const bool lazy_keep = h->lazy_recoff; h->lazy_recoff = false;
-	struct Restore { ngsqc_handle* h; bool v; ~Restore() { h->lazy_recoff = v; } } restore{h, lazy_keep};
-	stream_tiles(h, [&](const TileCtx& c) {
-		const int64_t n = c.n_rec;
-		if (n == 0) return true;
-		if (done + n > cap) throw ArgError("the verdict buffer is smaller than the number of records");
-		const int64_t* rec = ensure_recoff(h);
+	const int64_t done = for_each_tile_bytes(h, out, cap, "the verdict buffer is smaller than the number of records", [&](const TileCtx& c, const int64_t* rec, int64_t n) {
 		vb.run(c.infl, rec, n, 0, T, m, 0, VerdictOut{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}, s);
-		HIPCHK(hipMemcpyAsync(out + done, vb.vd.p, (size_t)n, hipMemcpyDeviceToHost, s)); HIPCHK(hipStreamSynchronize(s));
-		for (int64_t i = 0; i < n; ++i) out[done + i] &= 15;   // (the device's byte also holds the error code)
-		done += n;
-		return true;
+		return vb.vd.p;
 	});
+	for (int64_t i = 0; i < done; ++i) out[i] &= 15;   // (the device's byte also holds the error code)
 }
 } // namespace lib
 } // namespace ngsqc
