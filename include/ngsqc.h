@@ -200,6 +200,37 @@ int ngsqc_read_length_hist(ngsqc_handle* h, int64_t* out, int64_t cap);
  * for the first min(n_cycles, 320) cycles (per-cycle statistics only feed plots; longer reads are covered by the totals) */
 int ngsqc_read_cycle_stats(ngsqc_handle* h, int64_t* out, int64_t n_cycles);
 
+/* ---- raw-read QC of FASTQ text: FastqFileStream::readEntry + FastqEntry::validate (src/cppNGS/FastqFileStream.cpp:3-44, :133-156) and
+ * StatisticsReads::update(const FastqEntry&, ReadDirection) (src/cppNGS/StatisticsReads.cpp:26-81), the loop of ReadQC (src/ReadQC/main.cpp:57-96). An
+ * accumulator of its own, independent of any BAM handle. The caller inflates the file and feeds its TEXT in pieces cut anywhere (a piece and the carry in
+ * front of it stay below 2 GiB); the device finds the lines (the four lines of entry r are lines 4r .. 4r + 3 of the file, by the newline count alone),
+ * validates and counts every complete entry, and the rest waits as a carry in front of the next piece. direction: 0 forward, 1 reverse. last != 0 ends the
+ * file: the carry is flushed and the next feed starts a new file. The kernels of a piece run while the caller prepares the next one: feed returns before
+ * they end, and an error of piece k is reported by the feed of piece k + 1, by the last feed of the file or by ngsqc_fastq_result.
+ * Lines end with "\n" or "\r\n"; a file need not end with a newline; lines at the end of a file that are all empty are ignored; an incomplete last entry
+ * reads its missing lines as empty. An entry whose header line is empty is not validated and not counted in `entries` (FastqFileStream.cpp:151) but still
+ * counted in the statistics (main.cpp:63-66), when its bases are all ACGTN, its qualities are in range and both have one length - otherwise error kind 6.
+ * The first failing entry of the file, and within it the first check of validate that fails, makes feed return NGSQC_E_FORMAT with the reference's message
+ * (ngsqc_fastq_last_error); the accumulator is void from then on. kinds: 1 the header does not start with '@', 2 the second header is empty or does not
+ * start with '+', 3 bases and qualities differ in length, 4 a base outside ACGTN, 5 a quality character outside 33..74 (33..126 with long_read), 6 above. */
+typedef struct ngsqc_fastq ngsqc_fastq;
+typedef struct ngsqc_fastq_report {
+	int64_t entries;                      /* entries with a non-empty header in the current (or just ended) file: FastqFileStream::index() + 1 */
+	int64_t files;                        /* files begun */
+	int64_t err_file, err_entry;          /* the first error: ordinal of the file, entry in it (every entry counts), -1: none */
+	int32_t err_kind, reserved;
+	double h2d_ms, kernels_ms, wait_ms;   /* HIP-event sums of the copies and of the kernels; host time spent waiting for a piece in flight */
+} ngsqc_fastq_report;
+int  ngsqc_fastq_create(int32_t device, int32_t long_read, ngsqc_fastq** out);
+void ngsqc_fastq_destroy(ngsqc_fastq* f);
+const char* ngsqc_fastq_last_error(const ngsqc_fastq* f);   /* f NULL: the last failing ngsqc_fastq_create of this thread */
+int  ngsqc_fastq_feed(ngsqc_fastq* f, const uint8_t* text, int64_t n, int32_t direction, int32_t last);
+/* waits for the piece in flight; st as ngsqc_scan_reads fills it (n_unknown_base and n_quality_out_of_range stay 0: such entries are errors). Either may be NULL. */
+int  ngsqc_fastq_result(ngsqc_fastq* f, ngsqc_read_stats* st, ngsqc_fastq_report* rep);
+/* after ngsqc_fastq_result: as ngsqc_read_length_hist / ngsqc_read_cycle_stats */
+int  ngsqc_fastq_length_hist(ngsqc_fastq* f, int64_t* out, int64_t cap);
+int  ngsqc_fastq_cycle_stats(ngsqc_fastq* f, int64_t* out, int64_t n_cycles);
+
 /* ---- fused job: ONE pass over the BAM for every consumer --------------------------------------------------------------------
  * The reference re-reads the BAM for every pass of a tool: MappingQC runs Statistics::mapping*, then Statistics::contamination
  * (src/MappingQC/main.cpp:100-151), optionally StatisticsReads (-read_qc, :83-98) and Statistics::somaticCustomDepth

@@ -172,6 +172,11 @@ class ReadStats(C.Structure):
                 ("qscore_dist_r2", C.c_int64 * 60), ("max_cycles", C.c_int64), ("n_unknown_base", C.c_int64), ("n_quality_out_of_range", C.c_int64)]
 
 
+class FastqReport(C.Structure):
+    _fields_ = [("entries", C.c_int64), ("files", C.c_int64), ("err_file", C.c_int64), ("err_entry", C.c_int64), ("err_kind", C.c_int32), ("reserved", C.c_int32),
+                ("h2d_ms", C.c_double), ("kernels_ms", C.c_double), ("wait_ms", C.c_double)]
+
+
 def lib_path():
     return os.path.join(PKG_DIR, "libngsqc_hip.so")
 
@@ -240,6 +245,13 @@ def lib():
         L.ngsqc_scan_reads.restype = i32; L.ngsqc_scan_reads.argtypes = [vp, C.c_int32, C.POINTER(ReadStats)]
         L.ngsqc_read_length_hist.restype = i32; L.ngsqc_read_length_hist.argtypes = [vp, vp, i64]
         L.ngsqc_read_cycle_stats.restype = i32; L.ngsqc_read_cycle_stats.argtypes = [vp, vp, i64]
+        L.ngsqc_fastq_create.restype = i32; L.ngsqc_fastq_create.argtypes = [C.c_int32, C.c_int32, C.POINTER(vp)]
+        L.ngsqc_fastq_destroy.restype = None; L.ngsqc_fastq_destroy.argtypes = [vp]
+        L.ngsqc_fastq_last_error.restype = cp; L.ngsqc_fastq_last_error.argtypes = [vp]
+        L.ngsqc_fastq_feed.restype = i32; L.ngsqc_fastq_feed.argtypes = [vp, cp, i64, C.c_int32, C.c_int32]
+        L.ngsqc_fastq_result.restype = i32; L.ngsqc_fastq_result.argtypes = [vp, C.POINTER(ReadStats), C.POINTER(FastqReport)]
+        L.ngsqc_fastq_length_hist.restype = i32; L.ngsqc_fastq_length_hist.argtypes = [vp, vp, i64]
+        L.ngsqc_fastq_cycle_stats.restype = i32; L.ngsqc_fastq_cycle_stats.argtypes = [vp, vp, i64]
         L.ngsqc_open_shard.restype = i32; L.ngsqc_open_shard.argtypes = [cp, i32, i32, i32, C.POINTER(vp)]
         L.ngsqc_open_memory_shard.restype = i32; L.ngsqc_open_memory_shard.argtypes = [vp, C.c_size_t, i32, i32, i32, C.POINTER(vp)]
         L.ngsqc_comm_unique_id.restype = i32; L.ngsqc_comm_unique_id.argtypes = [vp]
@@ -312,6 +324,7 @@ EXPORTS = [
     "ngsqc_filter_pairs", "ngsqc_bgzf_compress", "ngsqc_bgzf_compress_level", "ngsqc_bam_to_fastq", "ngsqc_downsample", "ngsqc_downsample_keep",
     "ngsqc_extract_reads", "ngsqc_match_names", "ngsqc_remove_variants", "ngsqc_variant_verdicts",
     "ngsqc_clip_overlap", "ngsqc_clip_overlap_plan", "ngsqc_clean_haloplex", "ngsqc_haloplex_verdicts",
+    "ngsqc_fastq_create", "ngsqc_fastq_destroy", "ngsqc_fastq_last_error", "ngsqc_fastq_feed", "ngsqc_fastq_result", "ngsqc_fastq_length_hist", "ngsqc_fastq_cycle_stats",
 ]
 
 
@@ -900,6 +913,62 @@ class Handle:
 
 
 COMM_ID_BYTES = 128
+
+
+class FastqStats:
+    """Raw-read QC of FASTQ text on the device (include/ngsqc.h ngsqc_fastq_*): feed() takes the text of a file in pieces cut anywhere, result() returns the dict
+    Handle.scan_reads returns (layout of ngsqc_read_stats plus read_lengths and cycles) and sets .report. A failing entry raises NgsqcError (code -2) with the
+    reference's message; .report then names the file, the entry and the kind."""
+
+    FORWARD, REVERSE = 0, 1
+
+    def __init__(self, device=0, long_read=False):
+        self.h = C.c_void_p()
+        self.report = None
+        rc = lib().ngsqc_fastq_create(int(device), int(bool(long_read)), C.byref(self.h))
+        if rc != 0:
+            raise NgsqcError(rc, (lib().ngsqc_fastq_last_error(None) or b"").decode())
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().ngsqc_fastq_destroy(self.h); self.h = None
+
+    def __del__(self):
+        self.close()
+
+    def _chk(self, rc):
+        if rc != 0:
+            if rc == -2:
+                self._report()
+            raise NgsqcError(rc, (lib().ngsqc_fastq_last_error(self.h) or b"").decode("latin-1"))
+
+    def _report(self, st=None):
+        rep = FastqReport()
+        rc = lib().ngsqc_fastq_result(self.h, st, C.byref(rep))
+        self.report = {f: getattr(rep, f) for f, _ in FastqReport._fields_ if f != "reserved"}
+        return rc
+
+    def feed(self, text, direction=0, last=False):
+        text = bytes(text)
+        self._chk(lib().ngsqc_fastq_feed(self.h, text, len(text), int(direction), int(bool(last))))
+
+    def result(self, n_cycles=320):
+        st = ReadStats()
+        self._chk(self._report(C.byref(st)))
+        out = {f: (np.array(getattr(st, f), dtype=np.int64) if hasattr(getattr(st, f), "__len__") else int(getattr(st, f))) for f, _ in ReadStats._fields_}
+        out["read_lengths"] = self.length_hist(out["max_cycles"])
+        out["cycles"] = self.cycle_stats(n_cycles)
+        return out
+
+    def length_hist(self, max_cycles):
+        lens = np.zeros(int(max_cycles) + 1, dtype=np.int64)
+        self._chk(lib().ngsqc_fastq_length_hist(self.h, lens.ctypes.data, lens.size))
+        return lens
+
+    def cycle_stats(self, n_cycles=320):
+        cyc = np.zeros((int(n_cycles), 7), dtype=np.int64)
+        self._chk(lib().ngsqc_fastq_cycle_stats(self.h, cyc.ctypes.data, int(n_cycles)))
+        return cyc
 
 
 class Comm:

@@ -859,6 +859,20 @@ void StatisticsReads::update(BamReader& reader)
 	have_ = true;
 }
 
+void StatisticsReads::update(ngsqc_fastq* acc)
+{
+	ngsqc_fastq_report rep{};
+	const int rc = ngsqc_fastq_result(acc, &st_, &rep);
+	if (rc == NGSQC_E_FORMAT) NB_THROW(FileParseException, ngsqc_fastq_last_error(acc));                                                   // FastqEntry::validate
+	if (rc != NGSQC_OK) NB_THROW(ProgrammingException, ngsqc_fastq_last_error(acc));
+	read_lengths_.assign((size_t)st_.max_cycles + 1, 0);
+	if (ngsqc_fastq_length_hist(acc, read_lengths_.data(), (int64_t)read_lengths_.size()) != NGSQC_OK) NB_THROW(ProgrammingException, ngsqc_fastq_last_error(acc));
+	const int64_t n_cyc = std::min<int64_t>(st_.max_cycles, 320);
+	cycles_.assign((size_t)n_cyc * 7, 0);
+	if (n_cyc && ngsqc_fastq_cycle_stats(acc, cycles_.data(), n_cyc) != NGSQC_OK) NB_THROW(ProgrammingException, ngsqc_fastq_last_error(acc));
+	have_ = true;
+}
+
 bool StatisticsReads::takeFused(const std::string& bam_file)
 {
 	if (!(g_fused.ran && g_fused.have_reads && g_fused.bam == bam_file && g_fused.plan.single_end == single_end_)) return false;

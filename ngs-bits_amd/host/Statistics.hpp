@@ -98,6 +98,8 @@ class StatisticsReads
 public:
 	explicit StatisticsReads(bool single_end = false) : single_end_(single_end) {}
 	void update(BamReader& reader);
+	// ReadQC (src/ReadQC/main.cpp:57-96): every entry of the FASTQ files was fed to acc (ngsqc_fastq_feed: validation and update(const FastqEntry&) on the GPU)
+	void update(ngsqc_fastq* acc);
 	bool takeFused(const std::string& bam_file);   // the counts of the fused job announced with Statistics::planFused (false: none, run update())
 	QCCollection getResult();
 private:

@@ -5,6 +5,7 @@
 #include "Variant.hpp"
 #include "RmVariants.hpp"
 #include "ClipOverlap.hpp"
+#include "FastqReader.hpp"
 #include <cstring>
 using namespace ngsbits;
 
@@ -96,5 +97,28 @@ long long ngsbits_clip_summary(const long long* counts, char* out, long long cap
 	if (!lost.empty()) { if (err && err_cap > 0) { strncpy(err, lost.c_str(), (size_t)err_cap - 1); err[err_cap - 1] = 0; } return -1; }
 	if (out && cap > 0) { strncpy(out, text.c_str(), (size_t)cap - 1); out[cap - 1] = 0; }
 	return (long long)text.size();
+}
+// The text of a FASTQ file as ReadQC's reader delivers it (host/FastqReader.hpp: gzip with any number of members, BGZF, plain text), read in pieces of `piece`
+// bytes and laid end to end in out. Returns the length of the text (also when it exceeds cap: then out holds its first cap bytes), -1 on an error (message in
+// err). *n_pieces: the pieces delivered.
+long long ngsbits_fastq_text(const char* path, long long piece, unsigned char* out, long long cap, long long* n_pieces, char* err, int err_cap)
+{
+	try
+	{
+		if (piece <= 0) NB_THROW(ArgumentException, "piece size must be positive");
+		FastqTextReader r(path);
+		std::vector<uint8_t> buf((size_t)piece);
+		long long total = 0, pieces = 0;
+		for (;;)
+		{
+			const size_t n = r.read(buf.data(), buf.size());
+			if (n == 0) break;
+			if (total < cap) memcpy(out + total, buf.data(), (size_t)std::min<long long>((long long)n, cap - total));
+			total += (long long)n; ++pieces;
+		}
+		if (n_pieces) *n_pieces = pieces;
+		return total;
+	}
+	catch (std::exception& e) { return fail(e, err, err_cap); }
 }
 }
