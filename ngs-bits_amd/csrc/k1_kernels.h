@@ -130,8 +130,8 @@ struct LimTab
 // what zlib's inftrees.c checks of a set of code lengths: over-subscribed = error; incomplete = error unless it is a single code of length 1 (or no code at all)
 struct CodeShape
 {
-	int left = 1; uint32_t lmax = 0, total = 0; bool over = false;
-	K1_DEV void add(uint32_t l, uint32_t c) { left = (left << 1) - (int)c; over = over || left < 0; lmax = c ? l : lmax; total += c; }
+	int left = 1; uint32_t lmax = 0, total = 0; bool over = false;   // left: the Kraft sum's remainder; it goes negative (and stays so) once the set is over-subscribed - doubled by a multiplication, a shift of a negative value is undefined
+	K1_DEV void add(uint32_t l, uint32_t c) { left = left * 2 - (int)c; over = over || left < 0; lmax = c ? l : lmax; total += c; }
 	K1_DEV bool incomplete() const { return left > 0; }
 	K1_DEV bool ok() const { return !over && (left == 0 || lmax <= 1); }
 };
@@ -401,7 +401,7 @@ K1_KERNEL_OCC(64, P1_WAVES_PER_SIMD) void huff_tokens_kernel(const uint8_t* __re
 									uint32_t lim = (ccode + cnt) << (7 - l); if (lim > 0x80u) lim = 0x80u;
 									limC[l - 1] = lim | (((k - ccode) & 0xffffu) << 16);
 									ccode = (ccode + cnt) << 1; k += cnt;
-									cleft = (cleft << 1) - (int)cnt; if (cnt) cmax = (uint32_t)l;
+									cleft = cleft * 2 - (int)cnt; if (cnt) cmax = (uint32_t)l;
 								}
 								ccl_lo = 0; ccl_hi = 0;
 								#pragma nounroll
@@ -521,7 +521,7 @@ K1_KERNEL_OCC(64, P1_WAVES_PER_SIMD) void huff_tokens_kernel(const uint8_t* __re
 										const uint32_t v = L.linfo(l), ea = v & 511u, eb2 = (v >> 9) & 511u, ec = v >> 18, nl = ea - pa, nn = eb2 - pb;
 										L.linfo(l) = nl | ((pa & 255u) << 16) | (((pb - nl) & 255u) << 24);
 										if (nl + nn) last_non = nn != 0;
-										leftL = (leftL << 1) - (int)(nl + nn); leftD = (leftD << 1) - (int)(ec - pc);
+										leftL = leftL * 2 - (int)(nl + nn); leftD = leftD * 2 - (int)(ec - pc);
 										pa = ea; pb = eb2; pc = ec;
 									}
 									L.linfo(0) = last_non ? (((pb - 1u) & 255u) << 24) : (1u | (((pa - 1u) & 255u) << 16));   // the all-ones code: the last symbol of the longest length
