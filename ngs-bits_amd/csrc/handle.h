@@ -152,6 +152,8 @@ struct DepthSet
 
 // what a consumer sees of the resident tile (offsets are tile-local; byte 0 is the first carried byte)
 struct TileCtx { const uint8_t* infl; int64_t total; const int64_t* recoff; int64_t n_rec; int64_t ord_base; int tile; bool last; };
+// what start_tile_stream found (tiles.hip): not called / no tile / the single tile is resident / K1 of the first tiles is enqueued
+enum StreamStart { STREAM_NONE, STREAM_EMPTY, STREAM_RESIDENT, STREAM_QUEUED };
 }} // namespace ngsqc::lib
 
 using namespace ngsqc::lib;
@@ -189,8 +191,11 @@ struct ngsqc_handle
 	DevBuf<uint8_t> buf[MAX_TILE_BUFS]; int nbuf = 2;
 	int64_t max_tile_members = 0;   // tile buffers (tile t lives in buf[t % nbuf]): [pfx carried bytes right-aligned][members][64]
 	std::vector<hipEvent_t> ev_chunk;                  // 4 per chunk: p1 start/end, p2 start/end
-	std::vector<hipEvent_t> ev_tile;                   // 2 per tile: K1 done (status on the host), consumed
-	PinBuf<BlockStatus> p_status; PinBuf<int32_t> p_start; PinBuf<int64_t> p_next; PinBuf<unsigned long long> p_small;
+	std::vector<hipEvent_t> ev_tile;                   // 2 per tile: last phase 2 done (the decoder's statuses on the host: K2 may start), consumed
+	std::vector<hipEvent_t> ev_crc;                    // 1 per tile: last CRC launch done (the CRC verdicts on the host, p_status_crc)
+	PinBuf<BlockStatus> p_status, p_status_crc; PinBuf<int32_t> p_start; PinBuf<int64_t> p_next; PinBuf<unsigned long long> p_small;
+	DevBuf<unsigned long long> d_kind;                 // {records, sum of block_size} of the file's first records (index_tile's sample)
+	StreamStart stream_start = STREAM_NONE;            // what start_tile_stream found for the job that is being set up: stream_tiles goes on from there
 	// ---- the resident tile ----
 	bool decoded = false; int cur_tile = -1;
 	int64_t n_rec = 0; DevBuf<int64_t> d_recoff;
@@ -311,6 +316,17 @@ int open_impl(ngsqc_handle** out, const char* path, const void* bytes, size_t n,
 // ---- tiles.hip: the tile stream (K1 chunks, K2, the resident tile) ----
 const int64_t* ensure_recoff(ngsqc_handle* h);
 void sync_all(ngsqc_handle* h);
+// The front of stream_tiles, for a job that calls it before it sets up its consumers: layout, K1 of the first tiles enqueued (nothing for a resident single tile);
+// h->stream_start says which. What follows must reach stream_tiles or, when it throws, abort_tile_stream (StreamStartGuard)
+void start_tile_stream(ngsqc_handle* h);
+void abort_tile_stream(ngsqc_handle* h);
+struct StreamStartGuard
+{
+	ngsqc_handle* h;
+	explicit StreamStartGuard(ngsqc_handle* hd) : h(hd) { start_tile_stream(h); }
+	~StreamStartGuard() { if (h->stream_start == STREAM_QUEUED) abort_tile_stream(h); h->stream_start = STREAM_NONE; }   // (stream_tiles clears it when it takes over)
+	StreamStartGuard(const StreamStartGuard&) = delete; StreamStartGuard& operator=(const StreamStartGuard&) = delete;
+};
 // Visit every tile in file order with the tile resident in HBM; f returns false to stop early
 void stream_tiles(ngsqc_handle* h, const std::function<bool(const TileCtx&)>& f);
 void for_each_tile(ngsqc_handle* h, const std::function<bool(int)>& f);

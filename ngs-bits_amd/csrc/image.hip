@@ -616,7 +616,9 @@ void plan_layout_now(ngsqc_handle* h, bool early_pass = false)
 	h->p_status.ensure((size_t)nb);
 	while ((int64_t)h->ev_chunk.size() < 4 * h->nch) { hipEvent_t e; HIPCHK(hipEventCreate(&e)); h->ev_chunk.push_back(e); }
 	while ((int)h->ev_tile.size() < 2 * nt) { hipEvent_t e; HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming)); h->ev_tile.push_back(e); }
-	h->p_small.ensure(64); h->p_rb.ensure((size_t)ngsqc_handle::RB_TOTAL);
+	h->p_status_crc.ensure((size_t)nb);
+	while ((int)h->ev_crc.size() < nt) { hipEvent_t e; HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming)); h->ev_crc.push_back(e); }
+	h->p_small.ensure(64); h->p_rb.ensure((size_t)ngsqc_handle::RB_TOTAL); h->d_kind.ensure(2);
 	HIPCHK(hipStreamSynchronize(h->stream));   // the host vectors above go out of scope
 	h->tm.n_tiles = nt;
 	if (h->stream_img && early_pass) { stream_pass_begin(h); h->up->pass_fresh = true; }   // (ngsqc_open's layout thread: the copy starts now)

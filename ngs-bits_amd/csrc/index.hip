@@ -163,6 +163,21 @@ __global__ void index_init_kernel(const BlockDesc* __restrict__ blocks, int64_t 
 	start[b] = hi <= lo ? -1 : guess_all ? -2 : (hi <= exp0 ? -1 : (lo <= exp0 ? (int32_t)(exp0 - lo) : (assume0 && first_piece ? 0 : -2)));   // (an empty entry holds no record start)
 }
 
+// What kind of file this is (index_tile, the file's first tile): one thread follows the chain from exp0 over up to eight records and leaves {records, sum of their
+// block_size}. It stops at the end of the tile and at a block_size no record can have (K2 will say so). exp0 >= 0 and exp0 + 4 <= total are the caller's.
+__global__ void index_sample_kernel(const uint8_t* __restrict__ infl, int64_t total, int64_t exp0, unsigned long long* __restrict__ out)
+{
+	if (blockIdx.x != 0 || threadIdx.x != 0) return;
+	int64_t off = exp0; unsigned long long n = 0, sum = 0;
+	for (; n < 8 && off + 4 <= total; ++n)
+	{
+		const uint32_t bs = ld32u(infl + off);
+		if (bs < 32 || bs > (1u << 30)) break;
+		sum += bs; off += 4 + (int64_t)bs;
+	}
+	out[0] = n; out[1] = sum;
+}
+
 // The exact check of the walked chain on the device. Entries in front of the tile's first record (hi <= exp0) hold nothing; the entry that holds exp0 starts
 // there; every other start is a GUESS. The chain is right iff every walker leaves its entry exactly at the start of the next entry that has one, every entry
 // without a start lies wholly in front of that exit, and the last walker leaves the tile exactly at its end - or meets a record that the tile end cuts (it is
@@ -334,6 +349,11 @@ void launch_index_init(const BlockDesc* d_blocks, int64_t n_entries, int64_t pre
 	if (n_entries <= 0) return;
 	hipLaunchKernelGGL(index_init_kernel, dim3((int)((n_entries + 255) / 256)), dim3(256), 0, s, d_blocks, n_entries, prefix, ksh, nm, exp0, guess_all ? 1 : 0, assume0 ? 1 : 0, d_start); KCHECK();
 }
+void launch_index_sample(const uint8_t* d_infl, int64_t total, int64_t exp0, unsigned long long* d_out, hipStream_t s)
+{
+	hipLaunchKernelGGL(index_sample_kernel, dim3(1), dim3(64), 0, s, d_infl, total, exp0, d_out); KCHECK();
+}
+
 void launch_index_chain(const BlockDesc* d_blocks, int64_t n_entries, int64_t prefix, int ksh, int64_t nm, int64_t exp0, int64_t total, const int32_t* d_start, const int64_t* d_next, uint32_t* d_viol, long long* d_straddle, hipStream_t s)
 {
 	if (n_entries <= 0) return;

@@ -666,6 +666,9 @@ void run_job(ngsqc_handle* h, const ngsqc_job_desc* j, ngsqc_job_result* r, ngsq
 	h->tm.scan_ms = 0; h->tm.scan_kernel_ms = 0; h->tm.scan_launches = 0; h->tm.finalize_ms = 0; h->tm.depth_scan_ms = 0; h->tm.pileup_ms = 0; h->tm.reads_ms = 0; h->tm.scan_algorithmic_bytes = 0;   // (every per-consumer field of the previous job)
 	Timer total(h->stream); total.start();
 	ngsqc_handle::Partial local_map; ScanState dscan; PileupState pile; IndelState indel; ReadsState reads;
+	// K1 of the first tiles is enqueued before the consumers are set up: neither depends on the other, and the decoder runs on its own streams while the host uploads
+	// the region and site tables and clears the depth arrays (a set-up that throws takes the queued K1 down with it: the guard)
+	StreamStartGuard k1_ahead(h);
 	if (part) { delete h->partial; h->partial = new ngsqc_handle::Partial(); }
 	ngsqc_handle::Partial& map = part ? *h->partial : local_map;
 	if (do_map) { mapping_setup(h, j->mapping, map); map.scan.in_pass_fix = !part; map.scan.begin(h); }
@@ -753,6 +756,7 @@ void ngsqc_close(ngsqc_handle* h)
 	for (hipStream_t s : {h->stream, h->s_p1[0], h->s_p1[1], h->s_p2, h->s_crc}) if (s) (void)hipStreamDestroy(s);
 	for (hipEvent_t e : h->ev_chunk) (void)hipEventDestroy(e);
 	for (hipEvent_t e : h->ev_tile) (void)hipEventDestroy(e);
+	for (hipEvent_t e : h->ev_crc) (void)hipEventDestroy(e);
 	delete h->partial;
 	delete h;
 }

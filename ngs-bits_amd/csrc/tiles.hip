@@ -4,10 +4,16 @@
 // A BAM is processed as a STREAM OF TILES (contiguous BGZF-member ranges sized to HBM):
 //   * K1 runs as one continuous stream of member chunks over the whole file on its own HIP streams (Huffman phase of chunk
 //     c+1 overlaps the LZ77 phase of chunk c; the token scratch is a ring of four chunk slots), writing into one of three
-//     tile buffers, queued two tiles ahead of the tile the host works on;
+//     tile buffers, queued two tiles ahead of the tile the host works on. A job enqueues K1 of the first tiles BEFORE it sets up its consumers
+//     (start_tile_stream, called by run_job: region tables, depth arrays and site tables go up while the decoder already runs);
 //   * K2 (record index) and every consumer of a tile (mapping scan, depth scan, site pileup, raw-read QC) run on the handle's
 //     main stream while K1 already decodes the next tile: each member is inflated exactly once per job, and all consumers
 //     of a job see the tile while it is resident (ngsqc_run_job; the single-purpose entry points are jobs with one consumer).
+//     K2 of a tile waits for the event behind the tile's last PHASE 2 (ev_tile[2t], with the decoder's and resolver's statuses on the host), not for its CRC pass:
+//     the CRC32 launches of the tile's last chunks run beside K2 and the consumers on their own stream. Their verdict (ev_crc[t], a second copy of the statuses) is
+//     read by finish_crc_tile behind the enqueued consumers and before the tile counts as consumed - or, when K2 or a consumer throws, before that error counts: a
+//     CRC mismatch is the error a damaged tile reports, and nothing a job returns comes from a tile whose verdict has not been read. Phase 2 of tile t + 3 waits
+//     for the consumers AND the CRC pass of tile t (same buffer);
 //   * A record that straddles two tiles is carried: its head is copied right in front of the next tile's first member
 //     (a fixed prefix area in every tile buffer, so K1 of tile t+1 does not depend on K2 of tile t).
 // There is no CPU fallback anywhere in this file: without a HIP device every compute entry point fails with NGSQC_E_DEVICE.
@@ -46,7 +52,11 @@ void enqueue_k1_tile(ngsqc_handle* h, int t)
 		hipEvent_t* e4 = &h->ev_chunk[(size_t)(4 * c)];
 		uint32_t* const pool = h->d_tok.p + (size_t)(c % h->k1_slots) * (size_t)h->slot_pages * K1_PAGE_WORDS;
 		HIPCHK(hipStreamWaitEvent(h->s_p2, e4[1], 0));
-		if (c == cA && t >= h->nbuf) HIPCHK(hipStreamWaitEvent(h->s_p2, h->ev_tile[(size_t)(2 * (t - h->nbuf) + 1)], 0));   // the buffer's previous tile is consumed
+		if (c == cA && t >= h->nbuf)
+		{
+			HIPCHK(hipStreamWaitEvent(h->s_p2, h->ev_tile[(size_t)(2 * (t - h->nbuf) + 1)], 0));   // the buffer's previous tile is consumed
+			if (h->verify_crc) HIPCHK(hipStreamWaitEvent(h->s_p2, h->ev_crc[(size_t)(t - h->nbuf)], 0));   // ... and its CRC pass has read it (long done in practice)
+		}
 		HIPCHK(hipEventRecord(e4[2], h->s_p2));
 		launch_lz77_resolve(h->d_kdesc.p + c0, cn, out_base, h->d_status.p + c0, pool, h->d_tok_first.p + c0, h->d_tok_cnt.p + c0, h->d_comp.p, h->s_p2);
 		HIPCHK(hipEventRecord(e4[3], h->s_p2));
@@ -59,31 +69,55 @@ void enqueue_k1_tile(ngsqc_handle* h, int t)
 	};
 	for (int64_t c = cA; c < cB; ++c) { launch_p1(c); launch_p2(c); }
 	const int64_t f = h->tiles[(size_t)t].first, m = h->tiles[(size_t)t].second;
-	hipStream_t s_last = h->verify_crc ? crc_stream : h->s_p2;
-	HIPCHK(hipMemcpyAsync(h->p_status.p + f, h->d_status.p + f, (size_t)m * sizeof(BlockStatus), hipMemcpyDeviceToHost, s_last));
-	HIPCHK(hipEventRecord(h->ev_tile[(size_t)(2 * t)], s_last));
+	// the tile is ready for K2 and its consumers when its last phase 2 is done: they need the inflated bytes and the decoder's and resolver's verdicts (p_status).
+	// The CRC verdict comes behind the tile's last CRC launch in a copy of its own (p_status_crc, finish_crc_tile): the CRC pass of the last chunk runs beside K2
+	// (a CRC launch of an earlier chunk may already have marked a member in the first copy: finish_k1_tile leaves those marks to finish_crc_tile)
+	HIPCHK(hipMemcpyAsync(h->p_status.p + f, h->d_status.p + f, (size_t)m * sizeof(BlockStatus), hipMemcpyDeviceToHost, h->s_p2));
+	HIPCHK(hipEventRecord(h->ev_tile[(size_t)(2 * t)], h->s_p2));
+	if (h->verify_crc)
+	{
+		HIPCHK(hipMemcpyAsync(h->p_status_crc.p + f, h->d_status.p + f, (size_t)m * sizeof(BlockStatus), hipMemcpyDeviceToHost, crc_stream));
+		HIPCHK(hipEventRecord(h->ev_crc[(size_t)t], crc_stream));
+	}
 	h->tm.inflate_launches++;
 	h->k1_enq = h->tile_first_chunk[(size_t)t + 1];
 }
 
 // Wait for K1 of tile t, check every member; members whose token stream overflowed the clen + 64 budget (e.g. Huffman-only
 // streams of low-entropy data) get a second chance with a worst-case budget.
+// The CRC verdict of tile t: waits for the tile's CRC pass (enqueue_k1_tile's second event) and fails like htslib at the first member in [first, upto) whose
+// inflated bytes do not have the CRC32 of its trailer (upto < 0: the whole tile). Nothing of a tile counts before this has returned.
+void finish_crc_tile(ngsqc_handle* h, int t, int64_t upto)
+{
+	if (!h->verify_crc) return;
+	HIPCHK(hipEventSynchronize(h->ev_crc[(size_t)t]));
+	const int64_t f = h->tiles[(size_t)t].first, m = h->tiles[(size_t)t].second;
+	const BlockStatus* st = h->p_status_crc.p;
+	for (int64_t i = f, end = upto < 0 ? f + m : upto; i < end; ++i)
+		if (st[i].error == K1_ERR_CRC) throw FormatError(inflate_error(h, i, K1_ERR_CRC));
+}
+
 void finish_k1_tile(ngsqc_handle* h, int t)
 {
-	HIPCHK(hipEventSynchronize(h->ev_tile[(size_t)(2 * t)]));
+	HIPCHK(hipEventSynchronize(h->ev_tile[(size_t)(2 * t)]));   // the tile's last phase 2 (not its CRC pass: finish_crc_tile)
 	const int64_t f = h->tiles[(size_t)t].first, m = h->tiles[(size_t)t].second;
 	std::vector<int64_t> redo;
 	for (int64_t i = f; i < f + m; ++i)
 	{
 		const uint32_t e = h->p_status.p[i].error;
 		if (e == K1_ERR_TOKEN_OVERFLOW) redo.push_back(i);
-		else if (e) throw FormatError(inflate_error(h, i, e));
+		else if (e && e != K1_ERR_CRC)   // (a CRC mark that made it into this copy is read again, with all the others, by finish_crc_tile)
+		{
+			finish_crc_tile(h, t, i);   // the first failing member is the one reported: a CRC mismatch in front of this member comes first
+			throw FormatError(inflate_error(h, i, e));
+		}
 	}
 	h->tm.members_inflated += m;
 	if (redo.empty()) return;
 	std::vector<BlockDesc> desc; const uint64_t u_lo = h->blocks[(size_t)f].upos;
 	for (int64_t i : redo) { BlockDesc d = h->blocks[(size_t)i]; d.upos -= u_lo; desc.push_back(d); }
-	inflate_sync(h, redo, desc, h->buf[t % h->nbuf].p + h->pfx);
+	// (a member that fails its second chance is reported behind the tile's CRC mismatches, as when one status copy held both)
+	try { inflate_sync(h, redo, desc, h->buf[t % h->nbuf].p + h->pfx); } catch (...) { finish_crc_tile(h, t, -1); throw; }
 }
 
 // d_recoff of the tile that index_tile has just indexed (K2's write pass: the entry-relative offsets kept by the walk, expanded with coalesced stores)
@@ -130,14 +164,11 @@ void index_tile(ngsqc_handle* h, int t)
 		else if (!anchor_by_guess && exp0 >= 0 && exp0 + 4 <= total)
 		{
 			// (a sample, not one record: the mean block_size of up to eight records along the chain - an ONT file may well begin with a short read)
-			int64_t off = exp0, sum = 0; int n = 0;
-			for (; n < 8 && off + 4 <= total; ++n)
-			{
-				uint32_t bs = 0;
-				HIPCHK(hipMemcpyAsync(&bs, base + off, 4, hipMemcpyDeviceToHost, h->stream)); HIPCHK(hipStreamSynchronize(h->stream));
-				if (bs < 32 || bs > (1u << 30)) break;   // (not a record: K2 will say so)
-				sum += bs; off += 4 + (int64_t)bs;
-			}
+			// (one thread walks them on the device - it stops at a block_size that no record has: K2 will say so - and the host makes one round trip for {n, sum})
+			unsigned long long* ks = h->p_small.p + 48;
+			launch_index_sample(base, total, exp0, h->d_kind.p, h->stream);
+			HIPCHK(hipMemcpyAsync(ks, h->d_kind.p, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream)); HIPCHK(hipStreamSynchronize(h->stream));
+			const int64_t n = (int64_t)ks[0], sum = (int64_t)ks[1];
 			h->long_reads = n > 0 && sum / n > 8192;
 		}
 		h->lr_failures = 0;
@@ -342,25 +373,28 @@ void sync_all(ngsqc_handle* h)
 	(void)hipStreamSynchronize(h->s_p1[0]); (void)hipStreamSynchronize(h->s_p1[1]); (void)hipStreamSynchronize(h->s_p2); (void)hipStreamSynchronize(h->s_crc); (void)hipStreamSynchronize(h->stream);
 }
 
-// Visit every tile in file order with the tile resident in HBM (K1 + K2 done) while K1 of the next tile is already running.
-// A single-tile file that is already decoded is visited without redoing K1 / K2 (the reference re-reads the file for every
-// pass; a resident tile is kept). f returns false to stop early.
-void stream_tiles(ngsqc_handle* h, const std::function<bool(const TileCtx&)>& f)
+// The clean-up of a tile stream that ends in an exception, whoever threw: nothing stays queued, the stage intervals are dropped, no tile is resident
+void abort_tile_stream(ngsqc_handle* h)
 {
+	h->stream_start = STREAM_NONE;
+	if (h->stream_img) stream_pass_end(h);
+	sync_all(h); h->evlog->discard(); h->decoded = false; h->cur_tile = -1;
+}
+
+// The front of the tile stream: the layout, the counters of the chunk stream and K1 of the tiles that are queued ahead of the host (nothing here waits for a kernel).
+// A job calls it BEFORE it sets up its consumers (run_job): the decoder runs while the host uploads region tables and clears the depth arrays.
+// Leaves in h->stream_start what stream_tiles finds: STREAM_EMPTY (no tile), STREAM_RESIDENT (the single tile is decoded and indexed) or STREAM_QUEUED (K1 of the
+// first tiles is enqueued: what follows must reach stream_tiles or abort_tile_stream)
+void start_tile_stream(ngsqc_handle* h)
+{
+	h->stream_start = STREAM_NONE;
 	plan_layout(h);
 	dbg_stamp(h->sw.debug, "tile stream: layout ready");
 	const int nt = (int)h->tiles.size();
-	if (nt == 0) { h->decoded = true; h->n_rec = 0; return; }
-	if (nt == 1 && h->decoded && h->cur_tile == 0)
-	{
-		// (the tile may have been left by a job whose consumers never asked for the record offsets: this visitor may)
-		try { if (!h->lazy_recoff) ensure_recoff(h); f(resident_ctx(h)); } catch (...) { h->evlog->discard(); throw; }
-		h->evlog->resolve(); return;
-	}
+	if (nt == 0) { h->stream_start = STREAM_EMPTY; return; }
+	if (nt == 1 && h->decoded && h->cur_tile == 0) { h->stream_start = STREAM_RESIDENT; return; }
 	reset_decode_timings(h);
 	h->decoded = false; h->cur_tile = -1; h->k1_enq = 0; h->k2_plain = false;
-	const bool dbg = h->sw.debug;
-	const bool pipelined = h->sw.pipeline;   // 0: K1 of a tile starts only when the previous tile is consumed (stage attribution)
 	HIPCHK(hipMemsetAsync(h->d_work.p, 0, (size_t)h->nch * sizeof(unsigned long long), h->stream));
 	HIPCHK(hipMemsetAsync(h->d_pool_ctr.p, 0, (size_t)h->nch * sizeof(uint32_t), h->stream));
 	HIPCHK(hipStreamSynchronize(h->stream));
@@ -374,8 +408,34 @@ void stream_tiles(ngsqc_handle* h, const std::function<bool(const TileCtx&)>& f)
 	{
 		// K1 is queued nbuf - 1 tiles ahead of the tile the host works on (tile t + nbuf - 1 reuses the buffer of tile t - 1, whose consumers were
 		// queued - and their event recorded - in the previous iteration)
-		const int ahead = pipelined ? h->nbuf - 1 : 0;
+		const int ahead = h->sw.pipeline ? h->nbuf - 1 : 0;
 		for (int u = 0; u < std::min(nt, std::max(1, ahead)); ++u) enqueue_k1_tile(h, u);
+	}
+	catch (...) { abort_tile_stream(h); throw; }
+	h->stream_start = STREAM_QUEUED;
+	dbg_stamp(h->sw.debug, "tile stream: K1 of the first tiles enqueued");
+}
+
+// Visit every tile in file order with the tile resident in HBM (K1 phases 1 and 2 + K2 done, the CRC verdict read behind the enqueued consumers) while K1 of the
+// next tiles is already running. A single-tile file that is already decoded is visited without redoing K1 / K2 (the reference re-reads the file for every
+// pass; a resident tile is kept). f returns false to stop early.
+void stream_tiles(ngsqc_handle* h, const std::function<bool(const TileCtx&)>& f)
+{
+	if (h->stream_start == STREAM_NONE) start_tile_stream(h);   // (a job has done so before it set up its consumers)
+	const StreamStart st = h->stream_start; h->stream_start = STREAM_NONE;   // (from here on the catch below cleans up)
+	const int nt = (int)h->tiles.size();
+	if (st == STREAM_EMPTY) { h->decoded = true; h->n_rec = 0; return; }
+	if (st == STREAM_RESIDENT)
+	{
+		// the resident single tile (it may have been left by a job whose consumers never asked for the record offsets: this visitor may)
+		try { if (!h->lazy_recoff) ensure_recoff(h); f(resident_ctx(h)); } catch (...) { h->evlog->discard(); throw; }
+		h->evlog->resolve(); return;
+	}
+	const bool dbg = h->sw.debug;
+	const bool pipelined = h->sw.pipeline;   // 0: K1 of a tile starts only when the previous tile is consumed (stage attribution)
+	try
+	{
+		const int ahead = pipelined ? h->nbuf - 1 : 0;   // (tiles [0, max(1, ahead)) were enqueued by start_tile_stream)
 		for (int t = 0; t < nt; ++t)
 		{
 			const double d0 = wall_ms();
@@ -383,10 +443,14 @@ void stream_tiles(ngsqc_handle* h, const std::function<bool(const TileCtx&)>& f)
 			const double d1 = wall_ms();
 			finish_k1_tile(h, t);
 			const double d2 = wall_ms();
-			index_tile(h, t);
-			const double d3 = wall_ms();
-			const bool go_on = f(resident_ctx(h));
-			if (dbg) fprintf(stderr, "[ngsqc] tile %d/%d: enqueue next K1 %.2f ms, wait K1 %.2f ms, K2 %.2f ms, consumers %.2f ms (%lld records)\n", t, nt, d1 - d0, d2 - d1, d3 - d2, wall_ms() - d3, (long long)h->n_rec);
+			bool go_on = true; double d3 = d2;
+			// K2 and the consumers run on the decoder's verdicts alone, while the CRC pass of the tile's last chunk is still on its way. A damaged payload that is
+			// still a valid stream may make them fail first: the CRC verdict is read before their error counts, and a mismatch is the error that is reported
+			try { index_tile(h, t); d3 = wall_ms(); go_on = f(resident_ctx(h)); }
+			catch (...) { finish_crc_tile(h, t, -1); throw; }
+			const double d4 = wall_ms();
+			finish_crc_tile(h, t, -1);   // behind the enqueued consumers, before the tile counts: nothing a job returns comes from a tile without its verdict
+			if (dbg) fprintf(stderr, "[ngsqc] tile %d/%d: enqueue next K1 %.2f ms, wait K1 %.2f ms, K2 %.2f ms, consumers %.2f ms, wait CRC %.2f ms (%lld records)\n", t, nt, d1 - d0, d2 - d1, d3 - d2, d4 - d3, wall_ms() - d4, (long long)h->n_rec);
 			const bool stop = !go_on || t == h->shard_last_tile;   // (a shard stops at the tile that holds the first record of the next shard)
 			if (!stop && t + 1 < nt && h->carry_len > 0)
 				HIPCHK(hipMemcpyAsync(h->buf[(t + 1) % h->nbuf].p + h->pfx - h->carry_len, h->buf[t % h->nbuf].p + h->pfx - h->tile_prefix + h->carry_src, (size_t)h->carry_len, hipMemcpyDeviceToDevice, h->stream));
@@ -395,7 +459,7 @@ void stream_tiles(ngsqc_handle* h, const std::function<bool(const TileCtx&)>& f)
 			if (!pipelined && t + 1 < nt) { HIPCHK(hipStreamSynchronize(h->stream)); enqueue_k1_tile(h, t + 1); }
 		}
 	}
-	catch (...) { if (h->stream_img) stream_pass_end(h); sync_all(h); h->evlog->discard(); h->decoded = false; h->cur_tile = -1; throw; }
+	catch (...) { abort_tile_stream(h); throw; }
 	h->evlog->resolve();   // (index / scan / pileup stage times: HIP-event intervals that nobody waited for inside the loop)
 	if (h->stream_img)
 	{
