@@ -14,6 +14,7 @@
 // Statistics.cpp:45-53), which is exactly a prefix sum over these differences. All arithmetic is integer.
 #include "common.h"
 #include "rec.h"
+#include "baseq_bits.h"
 #include <algorithm>
 #include <cstring>
 #include <rocprim/device/device_radix_sort.hpp>
@@ -654,13 +655,11 @@ __global__ __launch_bounds__(256) void baseq_tile_kernel(const ScanParams p, lon
 					#pragma unroll
 					for (int k = 0; k < 16; ++k)
 					{
-						// bit 7 of a byte of y = (x | 0x80) - min_baseq is set iff the byte's low seven bits reach the threshold, bit 7 of x iff the byte is 128 or more
-						// (0xff: no quality): clear in both = below. The four flags (bits 7, 15, 23, 31) move to bits 21..24 of the product: no two terms meet in a bit
-						const uint32_t lt = (~(((w[k] | 0x80808080u) - thr) | w[k]) & 0x80808080u) >> 7;
-						mm |= (unsigned long long)(((lt * 0x00204081u) >> 21) & 15u) << (4 * k);
+						const uint32_t lt = bq_below4(w[k], thr);   // (baseq_bits.h: the bytes of a dword tested together)
+						mm |= (unsigned long long)lt << (4 * k);
 					}
 					const uint32_t left = nq - 64u * c;
-					low[c] = left >= 64u ? mm : mm & ((1ull << left) - 1ull);
+					low[c] = bq_keep_first(mm, left);
 				}
 			if (p.min_baseq > 127) { low[0] = low[1] = low[2] = low[3] = 0; }   // (a threshold the byte trick does not hold for: every base goes the byte way below)
 			long long ref_len = 0;
@@ -707,9 +706,7 @@ __global__ __launch_bounds__(256) void baseq_tile_kernel(const ScanParams p, lon
 							const uint32_t b_hi = by_byte ? a_lo : min(a_hi, BQ_BITS);
 							for (uint32_t cw = a_lo >> 6; cw * 64u < b_hi; ++cw)
 							{
-								unsigned long long m = cw == 0 ? low[0] : cw == 1 ? low[1] : cw == 2 ? low[2] : low[3];
-								if (a_lo > 64u * cw) m &= ~0ull << (a_lo - 64u * cw);
-								if (b_hi < 64u * cw + 64u) m &= (1ull << (b_hi - 64u * cw)) - 1ull;
+								unsigned long long m = bq_clip_word(cw == 0 ? low[0] : cw == 1 ? low[1] : cw == 2 ? low[2] : low[3], a_lo, b_hi, cw);
 								while (m) { const uint32_t bit = (uint32_t)__builtin_ctzll(m); m &= m - 1ull; masked(64u * cw + bit); }
 							}
 							for (uint32_t x = max(a_lo, b_hi); x < a_hi; ++x) if (q[x] < p.min_baseq) masked(x);   // (reads longer than BQ_BITS)
