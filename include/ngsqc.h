@@ -231,6 +231,46 @@ int  ngsqc_fastq_result(ngsqc_fastq* f, ngsqc_read_stats* st, ngsqc_fastq_report
 int  ngsqc_fastq_length_hist(ngsqc_fastq* f, int64_t* out, int64_t cap);
 int  ngsqc_fastq_cycle_stats(ngsqc_fastq* f, int64_t* out, int64_t n_cycles);
 
+/* ---- SeqPurge: adapter and quality trimming of paired-end reads (src/SeqPurge/AnalysisWorker.cpp:79-457, OutputWorker.cpp:36-77). An accumulator of its own,
+ * like ngsqc_fastq: the caller inflates the two files and feeds their TEXT in pieces cut anywhere, each side with its own carry. The pairs a feed processes
+ * are the entries complete on BOTH sides; the surplus of the side that is ahead waits. last != 0 ends the file pair (line structure as ngsqc_fastq: "\r\n",
+ * a missing final newline, empty lines at the end, an incomplete last entry). Per pair the device fills a plan record of 8 int32: len1_in, len2_in,
+ * insert_offset (-1: none), adapter_fwd (-1), adapter_rev (-1), len1_out, len2_out, flags (bit 0 / 1: read 1 / 2 quality-trimmed, bit 2 / 3: N-trimmed).
+ * With outputs set, the surviving entries are written as BGZF (valid gzip, EOF member at the end) deflated on the device: both reads >= min_len to out1 /
+ * out2; exactly one, when out3 is set, to out3_r1 or out3_r2; with ec the corrected bytes. Without outputs the plan is kept for ngsqc_purge_plan.
+ * The first failing pair (the lowest ordinal over all file pairs, every pair counts) makes feed return NGSQC_E_FORMAT; kinds, in the order they are looked
+ * for in a pair: 1 bases and qualities of a read differ in length (a message of this library's: the reference does not validate), 2 "Headers of reads do
+ * not match:", 3 "Could not convert base 'x' to complement!" (read 2), 4 "Read length unsupported! ..." (1000 and more); 0: "File X has more entries than
+ * Y!" at the end of a file pair (X, Y: ngsqc_purge_file_names, default in1 / in2). A byte of read 1 outside ACGTN matches nothing and is not N. create
+ * refuses (NGSQC_E_ARG) adapters shorter than 15 ("Forward adapter X too short!") or with bytes outside ACGTN, and qwin < 1. */
+typedef struct ngsqc_purge ngsqc_purge;
+typedef struct ngsqc_purge_params {
+	const char* a1; const char* a2;       /* forward / reverse adapter */
+	double match_perc, mep;
+	int32_t min_len, qcut, qwin, qoff, ncut, ec;
+} ngsqc_purge_params;
+typedef struct ngsqc_purge_stats {
+	int64_t pairs;                        /* pairs processed */
+	int64_t read_num, reads_trimmed_insert, reads_trimmed_adapter, reads_trimmed_q, reads_trimmed_n, reads_removed;   /* TrimmingStatistics (Auxilary.h:136-163) */
+	double  bases_perc_trim_sum;          /* summed in pair order */
+	int64_t bases_remaining[1000];        /* reads per length after trimming */
+	int64_t acons[2 * 40 * 5];            /* consensus pile-ups [adapter 1 / 2][position][A C G T N] */
+	int64_t ec_mismatch_r1[1000], ec_mismatch_r2[1000], ec_errors_per_read[1000];   /* ErrorCorrectionStatistics */
+	int64_t err_pair; int32_t err_kind, reserved;   /* the first error: pair ordinal (-1: none) and kind */
+	double  h2d_ms, index_ms, plan_ms, format_ms, deflate_ms, wait_ms;   /* HIP-event sums of the copies, the line index, the plan kernel and the format kernels (with their sizes and positions); host time of deflate and copy-out, and of waiting */
+} ngsqc_purge_stats;
+int  ngsqc_purge_create(int32_t device, const ngsqc_purge_params* params, ngsqc_purge** out);
+void ngsqc_purge_destroy(ngsqc_purge* p);
+const char* ngsqc_purge_last_error(const ngsqc_purge* p);   /* p NULL: the last failing ngsqc_purge_create of this thread */
+/* once, before the first feed; out3_r1 and out3_r2 both NULL (no singleton files) or both set; compression_level 0..9 */
+int  ngsqc_purge_outputs(ngsqc_purge* p, const char* out1, const char* out2, const char* out3_r1, const char* out3_r2, int32_t compression_level);
+int  ngsqc_purge_file_names(ngsqc_purge* p, const char* name1, const char* name2);   /* the names in "File X has more entries than Y!" from now on */
+int  ngsqc_purge_feed(ngsqc_purge* p, const uint8_t* text1, int64_t n1, const uint8_t* text2, int64_t n2, int32_t last);
+/* closes the outputs (no feed may follow) and fills st (may be NULL); after an error the statistics hold the feeds in front of the failing one */
+int  ngsqc_purge_result(ngsqc_purge* p, ngsqc_purge_stats* st);
+/* without outputs: the plan rows of pairs [first, first + n) into out[n][8] */
+int  ngsqc_purge_plan(ngsqc_purge* p, int64_t first, int64_t n, int32_t* out);
+
 /* ---- fused job: ONE pass over the BAM for every consumer --------------------------------------------------------------------
  * The reference re-reads the BAM for every pass of a tool: MappingQC runs Statistics::mapping*, then Statistics::contamination
  * (src/MappingQC/main.cpp:100-151), optionally StatisticsReads (-read_qc, :83-98) and Statistics::somaticCustomDepth

@@ -14,6 +14,6 @@ from .capi import (  # noqa: F401
     RmVariant, RmParams, RmCounts, RM_COUNT_NAMES, RMVAR_SNV, RMVAR_OTHER, RMVAR_INVALID, RMERR_NONE, RMERR_INVALID_LINE, RMERR_POS_NOT_FOUND, RMERR_BAD_BASE,
     ClipError, CLIP_MAPQ, CLIP_REMOVE, CLIP_BASEQ, CLIP_BASEN, CLIP_COUNT_NAMES, CLIP_PLAN_COLUMNS, CLIPERR_NONE, CLIPERR_ORIENT, CLIPERR_CIGAR_CHAR, CLIPERR_LENGTH, CLIPERR_SC_ORDER,
     CLIPERR_SC_START, CLIPERR_SC_END, CLIPERR_SC_INDEX, CLIPERR_SC_OP, CLIPERR_BAD_BASE, CLIPERR_UNSUPPORTED,
-    FastqStats, FastqReport,
+    FastqStats, FastqReport, Purge, PurgeParams, PurgeStats, purge_plan, PURGE_PLAN_COLUMNS,
 )
 from .dist import allreduce_counters, combine_counters_local, shard_blocks, scan_mapping_sharded, scan_mapping_sharded_local, scan_depth_sharded_local  # noqa: F401,E402

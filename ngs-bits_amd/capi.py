@@ -177,6 +177,24 @@ class FastqReport(C.Structure):
                 ("h2d_ms", C.c_double), ("kernels_ms", C.c_double), ("wait_ms", C.c_double)]
 
 
+class PurgeParams(C.Structure):
+    _fields_ = [("a1", C.c_char_p), ("a2", C.c_char_p), ("match_perc", C.c_double), ("mep", C.c_double), ("min_len", C.c_int32), ("qcut", C.c_int32),
+                ("qwin", C.c_int32), ("qoff", C.c_int32), ("ncut", C.c_int32), ("ec", C.c_int32)]
+
+
+class PurgeStats(C.Structure):
+    _fields_ = [("pairs", C.c_int64), ("read_num", C.c_int64), ("reads_trimmed_insert", C.c_int64), ("reads_trimmed_adapter", C.c_int64), ("reads_trimmed_q", C.c_int64),
+                ("reads_trimmed_n", C.c_int64), ("reads_removed", C.c_int64), ("bases_perc_trim_sum", C.c_double), ("bases_remaining", C.c_int64 * 1000),
+                ("acons", C.c_int64 * 400), ("ec_mismatch_r1", C.c_int64 * 1000), ("ec_mismatch_r2", C.c_int64 * 1000), ("ec_errors_per_read", C.c_int64 * 1000),
+                ("err_pair", C.c_int64), ("err_kind", C.c_int32), ("reserved", C.c_int32), ("h2d_ms", C.c_double), ("index_ms", C.c_double), ("plan_ms", C.c_double),
+                ("format_ms", C.c_double), ("deflate_ms", C.c_double), ("wait_ms", C.c_double)]
+
+
+PURGE_PLAN_COLUMNS = ("len1_in", "len2_in", "insert_offset", "adapter_fwd", "adapter_rev", "len1_out", "len2_out", "flags")
+PURGE_A1 = b"AGATCGGAAGAGCACACGTCTGAACTCCAGTCA"
+PURGE_A2 = b"AGATCGGAAGAGCGTCGTGTAGGGAAAGAGTGT"
+
+
 def lib_path():
     return os.path.join(PKG_DIR, "libngsqc_hip.so")
 
@@ -252,6 +270,14 @@ def lib():
         L.ngsqc_fastq_result.restype = i32; L.ngsqc_fastq_result.argtypes = [vp, C.POINTER(ReadStats), C.POINTER(FastqReport)]
         L.ngsqc_fastq_length_hist.restype = i32; L.ngsqc_fastq_length_hist.argtypes = [vp, vp, i64]
         L.ngsqc_fastq_cycle_stats.restype = i32; L.ngsqc_fastq_cycle_stats.argtypes = [vp, vp, i64]
+        L.ngsqc_purge_create.restype = i32; L.ngsqc_purge_create.argtypes = [C.c_int32, C.POINTER(PurgeParams), C.POINTER(vp)]
+        L.ngsqc_purge_destroy.restype = None; L.ngsqc_purge_destroy.argtypes = [vp]
+        L.ngsqc_purge_last_error.restype = cp; L.ngsqc_purge_last_error.argtypes = [vp]
+        L.ngsqc_purge_outputs.restype = i32; L.ngsqc_purge_outputs.argtypes = [vp, cp, cp, cp, cp, C.c_int32]
+        L.ngsqc_purge_file_names.restype = i32; L.ngsqc_purge_file_names.argtypes = [vp, cp, cp]
+        L.ngsqc_purge_feed.restype = i32; L.ngsqc_purge_feed.argtypes = [vp, cp, i64, cp, i64, C.c_int32]
+        L.ngsqc_purge_result.restype = i32; L.ngsqc_purge_result.argtypes = [vp, C.POINTER(PurgeStats)]
+        L.ngsqc_purge_plan.restype = i32; L.ngsqc_purge_plan.argtypes = [vp, i64, i64, vp]
         L.ngsqc_open_shard.restype = i32; L.ngsqc_open_shard.argtypes = [cp, i32, i32, i32, C.POINTER(vp)]
         L.ngsqc_open_memory_shard.restype = i32; L.ngsqc_open_memory_shard.argtypes = [vp, C.c_size_t, i32, i32, i32, C.POINTER(vp)]
         L.ngsqc_comm_unique_id.restype = i32; L.ngsqc_comm_unique_id.argtypes = [vp]
@@ -325,6 +351,7 @@ EXPORTS = [
     "ngsqc_extract_reads", "ngsqc_match_names", "ngsqc_remove_variants", "ngsqc_variant_verdicts",
     "ngsqc_clip_overlap", "ngsqc_clip_overlap_plan", "ngsqc_clean_haloplex", "ngsqc_haloplex_verdicts",
     "ngsqc_fastq_create", "ngsqc_fastq_destroy", "ngsqc_fastq_last_error", "ngsqc_fastq_feed", "ngsqc_fastq_result", "ngsqc_fastq_length_hist", "ngsqc_fastq_cycle_stats",
+    "ngsqc_purge_create", "ngsqc_purge_destroy", "ngsqc_purge_last_error", "ngsqc_purge_outputs", "ngsqc_purge_file_names", "ngsqc_purge_feed", "ngsqc_purge_result", "ngsqc_purge_plan",
 ]
 
 
@@ -969,6 +996,71 @@ class FastqStats:
         cyc = np.zeros((int(n_cycles), 7), dtype=np.int64)
         self._chk(lib().ngsqc_fastq_cycle_stats(self.h, cyc.ctypes.data, int(n_cycles)))
         return cyc
+
+
+class Purge:
+    """SeqPurge on the device (include/ngsqc.h ngsqc_purge_*): feed() takes the text of the two files in pieces cut anywhere, result() closes the outputs and
+    returns the statistics as a dict (arrays as numpy) and sets .stats. Without outputs the plan is kept: plan() returns (n, 8) int32 (PURGE_PLAN_COLUMNS).
+    A failing pair raises NgsqcError (code -2) with the reference's message; .error then holds (pair, kind)."""
+
+    def __init__(self, device=0, a1=PURGE_A1, a2=PURGE_A2, match_perc=80.0, mep=1e-6, min_len=30, qcut=15, qwin=5, qoff=33, ncut=7, ec=False):
+        self.h = C.c_void_p()
+        self.stats, self.error = None, None
+        p = PurgeParams(bytes(a1), bytes(a2), float(match_perc), float(mep), int(min_len), int(qcut), int(qwin), int(qoff), int(ncut), int(bool(ec)))
+        rc = lib().ngsqc_purge_create(int(device), C.byref(p), C.byref(self.h))
+        if rc != 0:
+            raise NgsqcError(rc, (lib().ngsqc_purge_last_error(None) or b"").decode("latin-1"))
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().ngsqc_purge_destroy(self.h); self.h = None
+
+    def __del__(self):
+        self.close()
+
+    def _chk(self, rc):
+        if rc != 0:
+            if rc == -2:
+                st = PurgeStats()
+                lib().ngsqc_purge_result(self.h, C.byref(st))
+                self.error = (int(st.err_pair), int(st.err_kind))
+            raise NgsqcError(rc, (lib().ngsqc_purge_last_error(self.h) or b"").decode("latin-1"))
+
+    def outputs(self, out1, out2, out3_prefix=None, compression_level=1):
+        o3 = (os.fsencode(out3_prefix + "_R1.fastq.gz"), os.fsencode(out3_prefix + "_R2.fastq.gz")) if out3_prefix else (None, None)
+        self._chk(lib().ngsqc_purge_outputs(self.h, os.fsencode(out1), os.fsencode(out2), o3[0], o3[1], int(compression_level)))
+
+    def file_names(self, name1, name2):
+        self._chk(lib().ngsqc_purge_file_names(self.h, os.fsencode(name1), os.fsencode(name2)))
+
+    def feed(self, text1, text2, last=False):
+        text1, text2 = bytes(text1), bytes(text2)
+        self._chk(lib().ngsqc_purge_feed(self.h, text1, len(text1), text2, len(text2), int(bool(last))))
+
+    def result(self):
+        st = PurgeStats()
+        self._chk(lib().ngsqc_purge_result(self.h, C.byref(st)))
+        out = {f: (np.array(getattr(st, f), dtype=np.int64) if hasattr(getattr(st, f), "__len__") else getattr(st, f)) for f, _ in PurgeStats._fields_ if f != "reserved"}
+        out["acons"] = out["acons"].reshape(2, 40, 5)
+        self.stats = out
+        return out
+
+    def plan(self, first=0, n=None):
+        if n is None:
+            n = self.result()["pairs"] - first
+        out = np.zeros((max(int(n), 1), 8), dtype=np.int32)
+        self._chk(lib().ngsqc_purge_plan(self.h, int(first), int(n), out.ctypes.data))
+        return out[:int(n)]
+
+
+def purge_plan(text1, text2, device=0, **params):
+    """The plan of SeqPurge alone for two whole FASTQ texts: (n, 8) int32, a row per pair (PURGE_PLAN_COLUMNS). No file is written."""
+    p = Purge(device=device, **params)
+    try:
+        p.feed(text1, text2, last=True)
+        return p.plan()
+    finally:
+        p.close()
 
 
 class Comm:

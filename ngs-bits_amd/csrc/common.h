@@ -94,6 +94,7 @@ void launch_index_write(const uint8_t* d_infl, int64_t total, const BlockDesc* d
 void launch_scan_counts(const uint32_t* d_cnt, int64_t n, int64_t* d_base, void* d_tmp, hipStream_t s);
 void launch_depth_prefix(int32_t* d_diff, int64_t n_slots, void* d_tmp, hipStream_t s);
 size_t scan_tmp_bytes(int64_t n);
+void launch_fastq_line_index(const uint8_t* d_text, size_t n, uint32_t* d_cnt, int64_t* d_base, void* d_tmp, uint32_t* d_lines, hipStream_t stream);   // fastqin.hip
 
 // ---- K3-K5 ----
 constexpr int GC_NMAX = 64;      // (bin, n) integer hit table for reads overlapping n < GC_NMAX GC chunks

@@ -64,6 +64,17 @@ __global__ void fq_result_kernel(const int64_t* __restrict__ total, const uint32
 	res[FR_LINES] = L; res[FR_ENTRIES] = E; res[FR_CARRY] = 4 * E <= L ? lines[4 * E] : n;
 }
 
+// The line index of n bytes of text (d_text padded to a multiple of FQ_BLOCK): d_lines[0 .. L] and the line count L in d_base[blocks], blocks = ceil(n / FQ_BLOCK).
+// d_cnt: blocks + 1, d_base: blocks + 2, d_tmp: scan_tmp_bytes(blocks) + 64, d_lines: n + 2. Shared with purge.hip.
+void launch_fastq_line_index(const uint8_t* d_text, size_t n, uint32_t* d_cnt, int64_t* d_base, void* d_tmp, uint32_t* d_lines, hipStream_t stream)
+{
+	const int64_t blocks = (int64_t)((n + FQ_BLOCK - 1) / FQ_BLOCK);
+	if (blocks) { hipLaunchKernelGGL(fq_count_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, d_text, (uint64_t)n, d_cnt); KCHECK(); }
+	launch_scan_counts(d_cnt, blocks, d_base, d_tmp, stream);
+	if (blocks) { hipLaunchKernelGGL(fq_lines_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, d_text, (uint64_t)n, d_base, d_lines); KCHECK(); }
+	else HIPCHK(hipMemsetAsync(d_lines, 0, sizeof(uint32_t), stream));
+}
+
 struct FqKernelArgs
 {
 	const uint8_t* text; const uint32_t* lines; const int64_t* total;
@@ -298,10 +309,7 @@ struct ngsqc_fastq
 		if (n) HIPCHK(hipMemcpyAsync(d_text.p, slot[cur].p, n, hipMemcpyHostToDevice, stream));
 		HIPCHK(hipEventRecord(ev[1], stream));
 		HIPCHK(hipMemsetAsync(d_misc.p + FM_LONG, 0, 8, stream));
-		if (blocks) { hipLaunchKernelGGL(fq_count_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, d_text.p, (uint64_t)n, d_cnt.p); KCHECK(); }
-		launch_scan_counts(d_cnt.p, blocks, d_base.p, d_tmp.p, stream);
-		if (blocks) { hipLaunchKernelGGL(fq_lines_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, d_text.p, (uint64_t)n, d_base.p, d_lines.p); KCHECK(); }
-		else HIPCHK(hipMemsetAsync(d_lines.p, 0, sizeof(uint32_t), stream));
+		launch_fastq_line_index(d_text.p, n, d_cnt.p, d_base.p, d_tmp.p, d_lines.p, stream);
 		hipLaunchKernelGGL(fq_result_kernel, dim3(1), dim3(1), 0, stream, d_base.p + blocks, d_lines.p, (uint64_t)n, last ? 1 : 0, d_res.p); KCHECK();
 		if (n)
 		{

@@ -1,0 +1,163 @@
+"""SeqPurge's per-pair text (ngs-bits_amd/csrc/purge_visit.h - what the GPU library compiles into the kernels of csrc/purge.hip) on the CPU, against the Python
+model (tests/seqpurge_oracle.py): the plan, the output text, the consensus pile-ups and the -ec histograms on the designed pairs (tests/purge_cases.py) and on
+the reference's inputs; the table of the binomial tail against exact integers; and the sweep that allows the kernel to count whole offsets."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import purge_cases as K
+import seqpurge_oracle as M
+from conftest import ROOT
+from test_cpu_seqpurge import REF_TESTS, read_in, ref_run
+
+EMUL = os.path.join(ROOT, "tests", "emul")
+CSRC = os.path.join(ROOT, "ngs-bits_amd", "csrc")
+NO_ERROR = (1 << 64) - 1
+
+
+@pytest.fixture(scope="module")
+def lib():
+    so = os.path.join(EMUL, "libpurge.so")
+    srcs = [os.path.join(EMUL, "purge_emul.cpp"), os.path.join(CSRC, "purge_visit.h"), os.path.join(CSRC, "fastq_visit.h")]
+    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
+        subprocess.check_call(["g++", "-O3", "-std=c++17", "-ffp-contract=off", "-shared", "-fPIC", "-Wall", "-Wno-unknown-pragmas", "-Wno-unused-function", "-o", so, srcs[0]])
+    L = C.CDLL(so)
+    L.purge_tail_size.restype = C.c_int32
+    L.purge_tail_table.argtypes = [C.c_void_p]
+    L.purge_sweep.restype = C.c_int64; L.purge_sweep.argtypes = [C.c_double]
+    L.purge_emul.restype = C.c_int32
+    L.purge_emul.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_uint64, C.c_char_p, C.c_char_p, C.c_double, C.c_double] + [C.c_void_p] * 2 + [C.c_int64] + [C.c_void_p] * 3
+    L.purge_format.restype = C.c_int64
+    L.purge_format.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64]
+    return L
+
+
+def prepared(text, last):
+    """what the accumulator does on the host before a piece reaches the device (as for ReadQC)"""
+    text = bytes(text)
+    if last and text and not text.endswith(b"\n"):
+        text += b"\n"
+    while True:
+        if text.endswith(b"\n") and (len(text) == 1 or text[-2:-1] == b"\n"):
+            text = text[:-1]
+        elif text.endswith(b"\r\n") and (len(text) == 2 or text[-3:-2] == b"\n"):
+            text = text[:-2]
+        else:
+            return text
+
+
+def int_params(P):
+    return np.array([P.min_len, P.qcut, P.qwin, P.qoff, P.ncut, int(P.ec)], np.int32)
+
+
+def emulate(L, text1, text2, P, last=True, outputs=True):
+    t1, t2 = (np.frombuffer(prepared(t, last), np.uint8).copy() for t in (text1, text2))
+    cap = max(len(t1), len(t2)) // 4 + 2
+    plan, acons, ec, out = np.zeros((cap, 8), np.int32), np.zeros(400, np.uint64), np.zeros(3000, np.uint64), np.zeros(4, np.uint64)
+    ip = int_params(P)
+    rc = L.purge_emul(t1.ctypes.data, len(t1), t2.ctypes.data, len(t2), int(last), 0, P.a1, P.a2, P.match_perc, P.mep, ip.ctypes.data, plan.ctypes.data, cap,
+                      acons.ctypes.data, ec.ctypes.data, out.ctypes.data)
+    assert rc == 0
+    n = int(out[0])
+    err = None if int(out[1]) == NO_ERROR else (int(out[1]) >> 8, int(out[1]) & 255)
+    texts = []
+    if outputs and err is None:
+        buf = np.zeros(len(t1) + len(t2) + 16, np.uint8)
+        for k in range(4):
+            got = L.purge_format(t1.ctypes.data, len(t1), t2.ctypes.data, len(t2), plan.ctypes.data, n, P.min_len, int(P.out3), k, buf.ctypes.data, len(buf))
+            assert got >= 0
+            texts.append(buf[:got].tobytes())
+    return dict(plan=plan[:n], acons=acons.astype(np.int64).reshape(2, 40, 5), ec=ec.astype(np.int64).reshape(3, 1000), err=err, out=texts, carry=(int(out[2]), int(out[3])))
+
+
+def same_as_model(got, r):
+    assert np.array_equal(got["plan"], r.plan), np.nonzero((got["plan"] != r.plan).any(axis=1))[0][:5]
+    assert got["out"] == r.out
+    assert np.array_equal(got["acons"], r.stats.acons)
+    assert np.array_equal(got["ec"], r.stats.ec)
+
+
+@pytest.mark.parametrize("variant", ["plain", "crlf", "no final newline"])
+def test_catalogue(lib, variant):
+    for g in K.catalogue():
+        t1, t2 = g.texts(crlf=variant == "crlf", final_newline=variant != "no final newline")
+        r = M.run(t1, t2, g.params(), literal=True)
+        assert r.error is None
+        same_as_model(emulate(lib, t1, t2, g.params()), r)
+
+
+@pytest.mark.parametrize("name", sorted(REF_TESTS))
+def test_reference_inputs(lib, name):
+    in1, in2, _, _, out3, kw = REF_TESTS[name]
+    same_as_model(emulate(lib, read_in(in1), read_in(in2), M.Params(out3=out3 is not None, **kw)), ref_run(name))
+
+
+def test_errors(lib):
+    for name, t1, t2, kind, pair, _ in K.error_cases():
+        assert emulate(lib, t1, t2, M.Params(), outputs=False)["err"] == (pair, kind), name
+
+
+def test_pairs_are_the_entries_complete_on_both_sides(lib):
+    g = K.catalogue()[0]
+    t1, t2 = g.texts()
+    n = len(g.cases)
+    cut2 = t2.rindex(b"@") + 3                      # side 2 stops inside its last header
+    got = emulate(lib, t1, t2[:cut2], g.params(), last=False, outputs=False)
+    assert len(got["plan"]) == n - 1
+    assert got["carry"] == (t1.rindex(b"@"), t2.rindex(b"@"))
+    assert np.array_equal(got["plan"], M.run(t1, t2, g.params()).plan[:n - 1])
+
+
+def test_tail_table_within_2_ulp(lib):
+    """every entry against the exact value (integers, one correctly rounded division)"""
+    tab = np.zeros(lib.purge_tail_size(), np.float64)
+    lib.purge_tail_table(tab.ctypes.data)
+    exact = np.zeros_like(tab)
+    at = 0
+    for n in range(1000):
+        c, s, row = 1, 0, [0.0] * (n + 1)          # c = C(n,i) 3^(n-i), from i = n down
+        den = 4 ** n
+        for i in range(n, -1, -1):
+            s += c
+            row[i] = s / den
+            c = c * 3 * i // (n - i + 1)
+        exact[at:at + n + 1] = row
+        at += n + 1
+    assert at == len(tab)
+    assert M.tail(10, 10) == exact[10 * 11 // 2 + 10] and M.tail(0, 0) == exact[0] == 1.0
+    ulps = np.abs(tab.view(np.int64) - exact.view(np.int64))
+    print("largest distance of the table from the exact tail: %d ulp" % ulps.max())
+    assert ulps.max() <= 2
+
+
+@pytest.mark.parametrize("match_perc", [80.0])
+def test_whole_counts_give_the_early_exit_verdict(lib, match_perc):
+    """pg_plan_kernel counts whole offsets and skips 'mismatches over budget'; the reference leaves its loop early and lets the percentage test skip. Exhaustive
+    over every state of an early exit with fewer than 1000 positions: the two verdicts never differ (at every match_perc the tests use: 80)."""
+    assert lib.purge_sweep(match_perc) == 0
+
+
+def test_stand_alone_under_sanitizers(tmp_path):
+    """the same text as a program of its own, built with AddressSanitizer and UBSan, over every group of the catalogue and the designed errors: the texts lie in
+    heap buffers of exactly their size, so a read or write outside a read, a plane or a table ends the run; its plan equals the model's"""
+    exe = str(tmp_path / "purge_emul_main")
+    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-Wno-unknown-pragmas", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                           "-o", exe, os.path.join(EMUL, "purge_emul_main.cpp")])
+
+    def run(t1, t2, P):
+        (tmp_path / "t1").write_bytes(prepared(t1, True)); (tmp_path / "t2").write_bytes(prepared(t2, True))
+        p = subprocess.run([exe, str(tmp_path / "t1"), str(tmp_path / "t2"), P.a1.decode(), P.a2.decode()] + [str(int(v)) for v in (P.min_len, P.qcut, P.qwin, P.qoff, P.ncut, P.ec, P.out3)],
+                           capture_output=True, text=True)
+        assert p.returncode == 0, p.stderr[-2000:]
+        return p.stdout.splitlines()
+    for g in K.catalogue():
+        t1, t2 = g.texts()
+        r = M.run(t1, t2, g.params())
+        lines = run(t1, t2, g.params())
+        assert [[int(v) for v in l.split()] for l in lines[:len(r.plan)]] == r.plan.tolist(), g.name
+        assert lines[len(r.plan):] == ["stream %d: %d bytes" % (k, len(r.out[k])) for k in range(4)], g.name
+    for name, t1, t2, kind, pair, _ in K.error_cases():
+        assert run(t1, t2, M.Params())[-1] == "error %d %d" % (pair, kind), name
