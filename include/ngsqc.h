@@ -271,6 +271,58 @@ int  ngsqc_purge_result(ngsqc_purge* p, ngsqc_purge_stats* st);
 /* without outputs: the plan rows of pairs [first, first + n) into out[n][8] */
 int  ngsqc_purge_plan(ngsqc_purge* p, int64_t first, int64_t n, int32_t* out);
 
+/* ---- the per-entry FASTQ-to-FASTQ tools: FastqTrim, FastqExtract, FastqExtractUMI, FastqConvert (src/<tool>/main.cpp). "Edit every entry of a FASTQ stream
+ * and write it again": an accumulator like ngsqc_purge. The caller inflates the input and feeds its TEXT in pieces cut anywhere; FastqExtractUMI has two
+ * inputs ("sides"), each with its own carry, and a feed processes the entries complete on both; the other operations have one (text2 NULL, n2 0). last != 0
+ * ends the input (line structure as ngsqc_fastq); with two sides the run ends silently at the shorter one. Per entry and side the device fills a plan record
+ * of 8 int32:
+ *   [0] keep     1: the entry is written, 0: dropped (the ranges below then describe the whole lines)
+ *   [1] ins_at   byte offset in the header line in front of which text is inserted
+ *   [2] ins_len  bytes inserted there (FastqExtractUMI: ":" cut1 "," cut2 ":" umi1 "," umi2, composed on the device from both reads; 0 otherwise)
+ *   [3] b_off    [4] b_len   the kept part of the bases line
+ *   [5] q_off    [6] q_len   the kept part of the quality line (the two lines may differ in length: only FastqExtract validates)
+ *   [7] q_delta  added to every kept quality byte, modulo 256 (FastqConvert: -31)
+ * No line ever grows: a range is cut to the line it lies in. With outputs set, the kept entries are written as BGZF (valid gzip, EOF member at the end)
+ * deflated on the device: header with the insertion, kept bases, line 3 as it is, kept qualities, each followed by "\n". Without outputs the plan is kept
+ * for ngsqc_fqedit_plan.
+ *   NGSQC_FQEDIT_TRIM     start, end, len, max_len (all >= 0): bases >= max_len > 0: unchanged; start or end > 0: dropped when bases <= start + end, else
+ *                         [start, bases - start - end) of both lines; then both cut to len > 0 when the bases are longer
+ *   NGSQC_FQEDIT_EXTRACT  ids from ngsqc_fqedit_ids; the id of an entry is its trimmed header without the first byte, up to the first space. Not listed:
+ *                         written only with invert. Listed without a length (-1): written only without invert. Listed with length >= 1: without invert,
+ *                         written cut to that length (a length beyond the read keeps the whole read). Length 0 or below -2: dropped. Every entry with a
+ *                         non-empty header is validated with the kinds 1..5 of ngsqc_fastq, long_read included: the first failing entry makes feed return NGSQC_E_FORMAT
+ *                         with the reference's message, and the accumulator is void from then on
+ *   NGSQC_FQEDIT_UMI      cut1, cut2 (>= 0): the first cut k bytes of the bases and quality lines of read k go (a shorter line becomes empty)
+ *   NGSQC_FQEDIT_CONVERT  every quality byte - 31 */
+enum { NGSQC_FQEDIT_TRIM = 0, NGSQC_FQEDIT_EXTRACT = 1, NGSQC_FQEDIT_UMI = 2, NGSQC_FQEDIT_CONVERT = 3 };
+typedef struct ngsqc_fqedit ngsqc_fqedit;
+typedef struct ngsqc_fqedit_params {
+	int32_t op, long_read;                /* NGSQC_FQEDIT_*; long_read: qualities up to 126 are valid, and a wave per entry in the plan of EXTRACT */
+	int32_t start, end, len, max_len;     /* TRIM */
+	int32_t cut1, cut2;                   /* UMI */
+	int32_t invert, reserved;             /* EXTRACT: -v */
+} ngsqc_fqedit_params;
+typedef struct ngsqc_fqedit_stats {
+	int64_t entries;                      /* entries read (per side) */
+	int64_t written[2], bytes[2];         /* entries and text bytes given to output stream 1 / 2 (counted with or without outputs) */
+	int64_t err_entry; int32_t err_kind, reserved;   /* the first failing entry (-1: none) and the kind of ngsqc_fastq */
+	double  h2d_ms, index_ms, plan_ms, format_ms, deflate_ms, wait_ms;   /* as ngsqc_purge_stats */
+} ngsqc_fqedit_stats;
+int  ngsqc_fqedit_create(int32_t device, const ngsqc_fqedit_params* params, ngsqc_fqedit** out);
+void ngsqc_fqedit_destroy(ngsqc_fqedit* e);
+const char* ngsqc_fqedit_last_error(const ngsqc_fqedit* e);   /* e NULL: the last failing ngsqc_fqedit_create of this thread */
+/* EXTRACT, once, before the first feed: n ids, their bytes one behind the other in names, lengths[i] the length column (-1: none; lengths NULL: none has one).
+ * A later duplicate of an id replaces the earlier one; an id with length -2 is as good as not listed. The table lives in device memory, open-addressed,
+ * hashed by the read-name hash of the mate join (NGSQC_NAME_HASH_BITS truncates it); a hash hit is confirmed by comparing the bytes. */
+int  ngsqc_fqedit_ids(ngsqc_fqedit* e, const void* names, const int32_t* name_len, const int32_t* lengths, int64_t n);
+/* once, before the first feed; out2 with UMI only (and then needed); compression_level 0..9 */
+int  ngsqc_fqedit_outputs(ngsqc_fqedit* e, const char* out1, const char* out2, int32_t compression_level);
+int  ngsqc_fqedit_feed(ngsqc_fqedit* e, const uint8_t* text1, int64_t n1, const uint8_t* text2, int64_t n2, int32_t last);
+/* closes the outputs (no feed may follow) and fills st (may be NULL) */
+int  ngsqc_fqedit_result(ngsqc_fqedit* e, ngsqc_fqedit_stats* st);
+/* without outputs: the plan rows of entries [first, first + n) into out[n][sides][8], sides = 2 for UMI and 1 otherwise */
+int  ngsqc_fqedit_plan(ngsqc_fqedit* e, int64_t first, int64_t n, int32_t* out);
+
 /* ---- fused job: ONE pass over the BAM for every consumer --------------------------------------------------------------------
  * The reference re-reads the BAM for every pass of a tool: MappingQC runs Statistics::mapping*, then Statistics::contamination
  * (src/MappingQC/main.cpp:100-151), optionally StatisticsReads (-read_qc, :83-98) and Statistics::somaticCustomDepth

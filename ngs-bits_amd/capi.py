@@ -190,6 +190,18 @@ class PurgeStats(C.Structure):
                 ("format_ms", C.c_double), ("deflate_ms", C.c_double), ("wait_ms", C.c_double)]
 
 
+class FqEditParams(C.Structure):
+    _fields_ = [("op", C.c_int32), ("long_read", C.c_int32), ("start", C.c_int32), ("end", C.c_int32), ("len", C.c_int32), ("max_len", C.c_int32),
+                ("cut1", C.c_int32), ("cut2", C.c_int32), ("invert", C.c_int32), ("reserved", C.c_int32)]
+
+
+class FqEditStats(C.Structure):
+    _fields_ = [("entries", C.c_int64), ("written", C.c_int64 * 2), ("bytes", C.c_int64 * 2), ("err_entry", C.c_int64), ("err_kind", C.c_int32), ("reserved", C.c_int32),
+                ("h2d_ms", C.c_double), ("index_ms", C.c_double), ("plan_ms", C.c_double), ("format_ms", C.c_double), ("deflate_ms", C.c_double), ("wait_ms", C.c_double)]
+
+
+FQEDIT_OPS = {"trim": 0, "extract": 1, "umi": 2, "convert": 3}
+FQEDIT_PLAN_COLUMNS = ("keep", "ins_at", "ins_len", "b_off", "b_len", "q_off", "q_len", "q_delta")
 PURGE_PLAN_COLUMNS = ("len1_in", "len2_in", "insert_offset", "adapter_fwd", "adapter_rev", "len1_out", "len2_out", "flags")
 PURGE_A1 = b"AGATCGGAAGAGCACACGTCTGAACTCCAGTCA"
 PURGE_A2 = b"AGATCGGAAGAGCGTCGTGTAGGGAAAGAGTGT"
@@ -278,6 +290,14 @@ def lib():
         L.ngsqc_purge_feed.restype = i32; L.ngsqc_purge_feed.argtypes = [vp, cp, i64, cp, i64, C.c_int32]
         L.ngsqc_purge_result.restype = i32; L.ngsqc_purge_result.argtypes = [vp, C.POINTER(PurgeStats)]
         L.ngsqc_purge_plan.restype = i32; L.ngsqc_purge_plan.argtypes = [vp, i64, i64, vp]
+        L.ngsqc_fqedit_create.restype = i32; L.ngsqc_fqedit_create.argtypes = [C.c_int32, C.POINTER(FqEditParams), C.POINTER(vp)]
+        L.ngsqc_fqedit_destroy.restype = None; L.ngsqc_fqedit_destroy.argtypes = [vp]
+        L.ngsqc_fqedit_last_error.restype = cp; L.ngsqc_fqedit_last_error.argtypes = [vp]
+        L.ngsqc_fqedit_ids.restype = i32; L.ngsqc_fqedit_ids.argtypes = [vp, cp, vp, vp, i64]
+        L.ngsqc_fqedit_outputs.restype = i32; L.ngsqc_fqedit_outputs.argtypes = [vp, cp, cp, C.c_int32]
+        L.ngsqc_fqedit_feed.restype = i32; L.ngsqc_fqedit_feed.argtypes = [vp, cp, i64, cp, i64, C.c_int32]
+        L.ngsqc_fqedit_result.restype = i32; L.ngsqc_fqedit_result.argtypes = [vp, C.POINTER(FqEditStats)]
+        L.ngsqc_fqedit_plan.restype = i32; L.ngsqc_fqedit_plan.argtypes = [vp, i64, i64, vp]
         L.ngsqc_open_shard.restype = i32; L.ngsqc_open_shard.argtypes = [cp, i32, i32, i32, C.POINTER(vp)]
         L.ngsqc_open_memory_shard.restype = i32; L.ngsqc_open_memory_shard.argtypes = [vp, C.c_size_t, i32, i32, i32, C.POINTER(vp)]
         L.ngsqc_comm_unique_id.restype = i32; L.ngsqc_comm_unique_id.argtypes = [vp]
@@ -352,6 +372,7 @@ EXPORTS = [
     "ngsqc_clip_overlap", "ngsqc_clip_overlap_plan", "ngsqc_clean_haloplex", "ngsqc_haloplex_verdicts",
     "ngsqc_fastq_create", "ngsqc_fastq_destroy", "ngsqc_fastq_last_error", "ngsqc_fastq_feed", "ngsqc_fastq_result", "ngsqc_fastq_length_hist", "ngsqc_fastq_cycle_stats",
     "ngsqc_purge_create", "ngsqc_purge_destroy", "ngsqc_purge_last_error", "ngsqc_purge_outputs", "ngsqc_purge_file_names", "ngsqc_purge_feed", "ngsqc_purge_result", "ngsqc_purge_plan",
+    "ngsqc_fqedit_create", "ngsqc_fqedit_destroy", "ngsqc_fqedit_last_error", "ngsqc_fqedit_ids", "ngsqc_fqedit_outputs", "ngsqc_fqedit_feed", "ngsqc_fqedit_result", "ngsqc_fqedit_plan",
 ]
 
 
@@ -1061,6 +1082,78 @@ def purge_plan(text1, text2, device=0, **params):
         return p.plan()
     finally:
         p.close()
+
+
+class FastqEdit:
+    """The per-entry FASTQ-to-FASTQ tools on the device (include/ngsqc.h ngsqc_fqedit_*). op: "trim", "extract", "umi" or "convert". feed() takes the text in pieces
+    cut anywhere (two texts for "umi"), result() closes the outputs and returns the statistics as a dict and sets .stats. Without outputs the plan is kept:
+    plan() returns (n, 8) int32 (FQEDIT_PLAN_COLUMNS), (n, 2, 8) for "umi". A failing entry of "extract" raises NgsqcError (code -2) with the reference's
+    message; .error then holds (entry, kind)."""
+
+    def __init__(self, op, device=0, long_read=False, start=0, end=0, len=0, max_len=0, cut1=0, cut2=0, invert=False):
+        self.h = C.c_void_p()
+        self.stats, self.error = None, None
+        self.sides = 2 if op == "umi" else 1
+        p = FqEditParams(FQEDIT_OPS[op], int(bool(long_read)), int(start), int(end), int(len), int(max_len), int(cut1), int(cut2), int(bool(invert)), 0)
+        rc = lib().ngsqc_fqedit_create(int(device), C.byref(p), C.byref(self.h))
+        if rc != 0:
+            raise NgsqcError(rc, (lib().ngsqc_fqedit_last_error(None) or b"").decode("latin-1"))
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().ngsqc_fqedit_destroy(self.h); self.h = None
+
+    def __del__(self):
+        self.close()
+
+    def _chk(self, rc):
+        if rc != 0:
+            if rc == -2:
+                st = FqEditStats()
+                lib().ngsqc_fqedit_result(self.h, C.byref(st))
+                self.error = (int(st.err_entry), int(st.err_kind))
+            raise NgsqcError(rc, (lib().ngsqc_fqedit_last_error(self.h) or b"").decode("latin-1"))
+
+    def ids(self, names, lengths=None):
+        """names: the ids as bytes; lengths: one per id, None or -1 for an id without a length column"""
+        names = [bytes(x) for x in names]
+        nl = np.array([len(x) for x in names], dtype=np.int32)
+        ln = None if lengths is None else np.array([-1 if v is None else int(v) for v in lengths], dtype=np.int32)
+        self._chk(lib().ngsqc_fqedit_ids(self.h, b"".join(names), nl.ctypes.data, None if ln is None else ln.ctypes.data, len(names)))
+
+    def outputs(self, out1, out2=None, compression_level=1):
+        self._chk(lib().ngsqc_fqedit_outputs(self.h, os.fsencode(out1), None if out2 is None else os.fsencode(out2), int(compression_level)))
+
+    def feed(self, text1, text2=None, last=False):
+        text1 = bytes(text1); text2 = None if text2 is None else bytes(text2)
+        self._chk(lib().ngsqc_fqedit_feed(self.h, text1, len(text1), text2, 0 if text2 is None else len(text2), int(bool(last))))
+
+    def result(self):
+        st = FqEditStats()
+        self._chk(lib().ngsqc_fqedit_result(self.h, C.byref(st)))
+        out = {f: ([int(v) for v in getattr(st, f)] if hasattr(getattr(st, f), "__len__") else getattr(st, f)) for f, _ in FqEditStats._fields_ if f != "reserved"}
+        self.stats = out
+        return out
+
+    def plan(self, first=0, n=None):
+        if n is None:
+            n = self.result()["entries"] - first
+        out = np.zeros((max(int(n), 1), self.sides, 8), dtype=np.int32)
+        self._chk(lib().ngsqc_fqedit_plan(self.h, int(first), int(n), out.ctypes.data))
+        return out[:int(n)] if self.sides == 2 else out[:int(n), 0]
+
+
+def fastq_edit_plan(text1, text2=None, device=0, ids=None, **params):
+    """The plan of a per-entry FASTQ tool alone for whole FASTQ texts: (n, 8) int32, a row per entry (FQEDIT_PLAN_COLUMNS); (n, 2, 8) with two texts. No file is
+    written. params: op and the parameters of FastqEdit; ids: (names, lengths) for "extract"."""
+    e = FastqEdit(device=device, **params)
+    try:
+        if ids is not None:
+            e.ids(*ids)
+        e.feed(text1, text2, last=True)
+        return e.plan()
+    finally:
+        e.close()
 
 
 class Comm:

@@ -1,0 +1,492 @@
+// One or two FASTQ texts in device memory -> the per-entry FASTQ-to-FASTQ tools (src/FastqTrim, src/FastqExtract, src/FastqExtractUMI, src/FastqConvert): every
+// entry is edited and written again.
+//   line index  the kernels of fastqin.hip (launch_fastq_line_index), once per side. Entry r is lines 4r .. 4r + 3 of its side.
+//   plan        one record of 8 int32 per entry and side (fqedit_visit.h): keep, the insertion into the header, the kept ranges of the bases and quality lines,
+//               the quality delta. fe_plan_kernel: ONE LANE PER ENTRY where the plan is arithmetic on the line lengths (Trim, Convert, UMI; UMI looks for the first
+//               space of the header). fe_extract_kernel validates every cycle and looks the id up in the table: a lane per entry as ex_match_kernel does for
+//               short reads, ONE WAVE PER ENTRY with long_read (lanes striding over the cycles, lane 0 hashes the id and probes).
+//   id table    FastqExtract: open-addressed slots {hash, id index} of a power of two and at least twice the ids, linear probing, hashed by join.h's name_hash
+//               (NGSQC_NAME_HASH_BITS truncates it); offset, length and payload per id in arrays of their own. The host resolves duplicates before the upload, so
+//               insertion is a compare-and-swap per id and nothing else; a hash hit is confirmed by the length and the bytes.
+//   format      fe_sizes_kernel (the bytes an entry gives its stream; the counters of the statistics) -> BgzfStream::place -> fe_format_kernel: one wave per
+//               entry writes the bytes of the entry that fall inside the stream's window (fe_entry_byte); the windows are deflated on the device.
+// The accumulator (ngsqc_fqedit) takes the texts in pieces cut anywhere, as ngsqc_purge does: the entries of a feed are those complete on every side, the rest
+// waits as the side's carry.
+#include "join.h"
+#include "fqedit_visit.h"
+#include <unordered_map>
+
+namespace ngsqc {
+namespace {
+constexpr uint64_t FE_SLOT_EMPTY = ~0ull;
+struct FeSide { const uint8_t* text; const uint32_t* lines; uint64_t L; };
+struct FeTable { const ulonglong2* slots; uint64_t slot_mask, hash_mask; const uint8_t* bytes; const uint64_t* id_off; const uint32_t* id_len; const int32_t* payload; };
+struct FeArgs { FeSide s[2]; int sides; int64_t n; unsigned long long entry_base; FeParams P; int32_t* plan; unsigned long long* err; FeTable t; };
+
+__device__ __forceinline__ int32_t fe_lookup(const FeTable& t, const uint8_t* id, uint32_t len)
+{
+	if (!t.slots || !len) return FE_ABSENT;   // (the empty id is never listed)
+	const uint64_t h = name_hash(id, (int)len) & t.hash_mask;
+	for (uint64_t s = h & t.slot_mask;; s = (s + 1) & t.slot_mask)
+	{
+		const ulonglong2 e = t.slots[s];
+		if (e.y == FE_SLOT_EMPTY) return FE_ABSENT;
+		if (e.x != h || t.id_len[e.y] != len) continue;
+		const uint8_t* p = t.bytes + t.id_off[e.y];
+		bool same = true;
+		for (uint32_t i = 0; i < len && same; ++i) same = p[i] == id[i];
+		if (same) return t.payload[e.y];
+	}
+}
+} // namespace
+
+// slots: all words FE_SLOT_EMPTY; the ids are distinct
+__global__ __launch_bounds__(256) void fe_insert_kernel(const uint64_t* __restrict__ id_off, const uint32_t* __restrict__ id_len, int64_t n, const uint8_t* __restrict__ bytes,
+                                                        uint64_t hash_mask, uint64_t slot_mask, unsigned long long* slots /* [slot][2] */)
+{
+	const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+	for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
+	{
+		const uint64_t h = name_hash(bytes + id_off[i], (int)id_len[i]) & hash_mask;
+		for (uint64_t s = h & slot_mask;; s = (s + 1) & slot_mask)
+			if (atomicCAS(&slots[2 * s + 1], (unsigned long long)FE_SLOT_EMPTY, (unsigned long long)i) == FE_SLOT_EMPTY) { slots[2 * s] = h; break; }   // (the hash word is read behind this kernel only)
+	}
+}
+
+// Trim, Convert, UMI: a lane per entry
+__global__ __launch_bounds__(256) void fe_plan_kernel(const FeArgs a)
+{
+	const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+	for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < a.n; r += stride)
+	{
+		const FqEntry e = fq_entry(a.s[0].text, a.s[0].lines, a.s[0].L, (uint64_t)r);
+		int32_t* row = a.plan + (int64_t)FE_PLAN * a.sides * r;
+		if (a.P.op == FE_OP_TRIM) fe_plan_trim(row, a.P, e.bases.len, e.quals.len);
+		else if (a.P.op == FE_OP_CONVERT) fe_plan_convert(row, e.bases.len, e.quals.len);
+		else
+		{
+			const FqEntry e2 = fq_entry(a.s[1].text, a.s[1].lines, a.s[1].L, (uint64_t)r);
+			const uint32_t ins = fe_umi_len(fe_umi_of(a.s[0].text, e, a.s[1].text, e2, a.P.cut1, a.P.cut2));
+			fe_plan_umi(row, a.s[0].text, e, (uint32_t)a.P.cut1, ins);
+			fe_plan_umi(row + FE_PLAN, a.s[1].text, e2, (uint32_t)a.P.cut2, ins);
+		}
+	}
+}
+
+// Extract: NL lanes per entry (1, or the 64 of a wave). The first failing (entry, kind) by atomicMin, as fq_entry_kernel leaves it.
+template <int NL> __global__ __launch_bounds__(256) void fe_extract_kernel(const FeArgs a)
+{
+	const uint32_t lane = NL == 64 ? (threadIdx.x & 63u) : 0u;
+	const int64_t unit = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / NL, n_units = ((int64_t)gridDim.x * blockDim.x) / NL;
+	const uint8_t* __restrict__ text = a.s[0].text;
+	for (int64_t r = unit; r < a.n; r += n_units)   // (with NL = 64 r is the same in every lane of a wave: the ballots below see whole waves)
+	{
+		const FqEntry e = fq_entry(text, a.s[0].lines, a.s[0].L, (uint64_t)r);
+		uint32_t kind = fe_entry_kind(text, e);
+		if (!kind && e.header.len)
+		{
+			const uint8_t* __restrict__ b = text + e.bases.start; const uint8_t* __restrict__ q = text + e.quals.start;
+			uint32_t bad = 0;
+			for (uint32_t i = lane; i < e.bases.len; i += NL) bad |= fe_cycle_bad(b[i], q[i], a.P.long_read);
+			bool bb = bad & 1u, bq = bad & 2u;
+			if (NL == 64) { bb = __builtin_amdgcn_ballot_w64(bb) != 0; bq = __builtin_amdgcn_ballot_w64(bq) != 0; }
+			kind = fq_char_kind(false, bb, bq);
+		}
+		if (lane == 0)
+		{
+			if (kind) atomicMin(a.err, fq_error_word(a.entry_base + (unsigned long long)r, kind));
+			uint32_t at, len; fe_id_range(text, e.header, at, len);
+			fe_plan_extract(a.plan + (int64_t)FE_PLAN * r, fe_lookup(a.t, text + at, len), a.P.invert, e.bases.len, e.quals.len);
+		}
+	}
+}
+
+// sz[k][r]: the bytes entry r gives stream k (stream k takes side k); counts[k] / counts[2 + k]: entries and bytes of stream k
+__global__ __launch_bounds__(256) void fe_sizes_kernel(const FeArgs a, uint64_t* __restrict__ sz0, uint64_t* __restrict__ sz1, unsigned long long* __restrict__ counts)
+{
+	const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+	const int64_t rounds = (a.n + stride - 1) / stride;   // (every lane of a wave makes the same number of rounds: the wave sums see whole waves)
+	int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	long long c[2] = {0, 0}, b[2] = {0, 0};
+	for (int64_t i = 0; i < rounds; ++i, r += stride)
+	{
+		if (r >= a.n) continue;
+		for (int k = 0; k < a.sides; ++k)
+		{
+			const int32_t* row = a.plan + FE_PLAN * ((int64_t)a.sides * r + k);
+			const uint64_t n = fe_entry_bytes(row, fq_entry(a.s[k].text, a.s[k].lines, a.s[k].L, (uint64_t)r));
+			(k ? sz1 : sz0)[r] = n;
+			c[k] += row[FE_KEEP] ? 1 : 0; b[k] += (long long)n;
+		}
+	}
+	for (int k = 0; k < 2; ++k)
+	{
+		const long long wc = wave_sum(c[k]), wb = wave_sum(b[k]);
+		if ((threadIdx.x & 63) == 0) { if (wc) atomicAdd(&counts[k], (unsigned long long)wc); if (wb) atomicAdd(&counts[2 + k], (unsigned long long)wb); }
+	}
+}
+
+// one wave per entry of stream k: the bytes of the entry that fall inside the window
+__global__ __launch_bounds__(256) void fe_format_kernel(const FeArgs a, int k, const uint64_t* __restrict__ sz, const uint64_t* __restrict__ off, int64_t ws, Win w)
+{
+	const int lane = threadIdx.x & 63;
+	const int64_t nw = ((int64_t)gridDim.x * blockDim.x) >> 6;
+	const uint8_t* __restrict__ text = a.s[k].text;
+	for (int64_t r = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6; r < a.n; r += nw)
+	{
+		const int64_t size = (int64_t)sz[r];
+		if (!size) continue;
+		const int64_t pos = (int64_t)off[r] - ws;
+		const int64_t lo = max(pos, w.lo), hi = min(pos + size, w.hi);
+		if (lo >= hi) continue;
+		const FqEntry e = fq_entry(text, a.s[k].lines, a.s[k].L, (uint64_t)r);
+		const int32_t* row = a.plan + FE_PLAN * ((int64_t)a.sides * r + k);
+		FeUmi u{};
+		if (a.P.op == FE_OP_UMI)
+			u = fe_umi_of(a.s[0].text, k == 0 ? e : fq_entry(a.s[0].text, a.s[0].lines, a.s[0].L, (uint64_t)r), a.s[1].text, k == 1 ? e : fq_entry(a.s[1].text, a.s[1].lines, a.s[1].L, (uint64_t)r), a.P.cut1, a.P.cut2);
+		for (int64_t x = lo + lane; x < hi; x += 64) w.base[x] = fe_entry_byte(text, e, row, (uint64_t)(x - pos), u);
+	}
+}
+} // namespace ngsqc
+
+// ---------------------------------------------------------------- the accumulator behind the C ABI
+using namespace ngsqc::lib;
+
+struct ngsqc_fqedit
+{
+	int device = 0; hipStream_t stream = nullptr; std::string err; bool failed = false;
+	FeParams P{}; int sides = 1; const char* tool = "FastqTrim"; CallSwitches sw;
+	struct Side
+	{
+		std::vector<uint8_t> text;   // the carry, then what was fed
+		size_t n_idx = 0; int64_t blocks = 0; unsigned long long L = 0, E = 0;
+		DevBuf<uint8_t> d_text, d_tmp; DevBuf<uint32_t> d_cnt, d_lines; DevBuf<int64_t> d_base;
+	} side[2];
+	// the id table
+	DevBuf<uint8_t> d_id_bytes; DevBuf<uint64_t> d_id_off; DevBuf<uint32_t> d_id_len; DevBuf<int32_t> d_id_payload; DevBuf<ulonglong2> d_slots; uint64_t slot_mask = 0; bool has_ids = false;
+	DevBuf<int32_t> d_plan; DevBuf<unsigned long long> d_err, d_counts;
+	DevBuf<uint64_t> d_sz[2], d_off[2]; DevBuf<uint8_t> d_scan_tmp;
+	std::unique_ptr<BgzfStream> out[2]; std::string out_path[2]; bool has_out = false, finished = false;
+	std::vector<int32_t> all_plan;
+	ngsqc_fqedit_stats st{};
+	hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+	std::unique_ptr<StageClock> fmt_clock;
+
+	~ngsqc_fqedit()
+	{
+		(void)hipSetDevice(device);
+		if (stream) (void)hipStreamSynchronize(stream);
+		for (auto& o : out) o.reset();
+		fmt_clock.reset();
+		if (stream) (void)hipStreamDestroy(stream);
+		for (auto& e : ev) if (e) (void)hipEventDestroy(e);
+	}
+	void init(int dev, const ngsqc_fqedit_params* p)
+	{
+		if (!p) throw ArgError("ngsqc_fqedit_create: no parameters");
+		static const char* names[4] = {"FastqTrim", "FastqExtract", "FastqExtractUMI", "FastqConvert"};
+		if (p->op < 0 || p->op > 3) throw ArgError("ngsqc_fqedit_create: no such operation: " + std::to_string(p->op));
+		if (p->start < 0 || p->end < 0 || p->len < 0 || p->max_len < 0) throw ArgError("start, end, len and max_len must not be negative!");
+		if (p->cut1 < 0 || p->cut2 < 0) throw ArgError("cut1 and cut2 must not be negative!");
+		P.op = p->op; P.long_read = p->long_read ? 1 : 0; P.start = p->start; P.end = p->end; P.len = p->len; P.max_len = p->max_len; P.cut1 = p->cut1; P.cut2 = p->cut2; P.invert = p->invert ? 1 : 0;
+		sides = P.op == FE_OP_UMI ? 2 : 1; tool = names[P.op];
+		int n_dev = 0;
+		if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) throw std::runtime_error("no HIP device available (libngsqc_hip has no CPU fallback)");
+		if (dev < 0 || dev >= n_dev) throw ArgError("no such device");
+		device = dev; st.err_entry = -1;
+		HIPCHK(hipSetDevice(device));
+		HIPCHK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+		for (auto& e : ev) HIPCHK(hipEventCreate(&e));
+		fmt_clock.reset(new StageClock(true, stream));
+		d_err.alloc(1); d_counts.alloc(4);
+		HIPCHK(hipMemsetAsync(d_err.p, 0xff, 8, stream)); HIPCHK(hipMemsetAsync(d_counts.p, 0, 4 * 8, stream));
+		HIPCHK(hipStreamSynchronize(stream));
+	}
+	void ids(const uint8_t* names, const int32_t* name_len, const int32_t* lengths, int64_t n)
+	{
+		if (P.op != FE_OP_EXTRACT) throw ArgError("ngsqc_fqedit_ids: only FastqExtract takes ids");
+		if (has_ids || st.entries) throw ArgError("ngsqc_fqedit_ids: the ids are set once, before the first feed");
+		if (n < 0 || (n && (!names || !name_len))) throw ArgError("ngsqc_fqedit_ids: invalid ids");
+		HIPCHK(hipSetDevice(device));
+		// QHash::insert (main.cpp:51): a later duplicate replaces the earlier one
+		std::unordered_map<std::string, int32_t> m;
+		uint64_t o = 0;
+		for (int64_t i = 0; i < n; ++i)
+		{
+			if (name_len[i] < 0) throw ArgError("negative id length");
+			m[std::string((const char*)names + o, (size_t)name_len[i])] = lengths ? lengths[i] : FE_NO_LENGTH;
+			o += (uint64_t)name_len[i];
+		}
+		std::vector<uint8_t> bytes; std::vector<uint64_t> off; std::vector<uint32_t> len; std::vector<int32_t> payload;
+		for (auto& kv : m)
+		{
+			if (kv.second == FE_ABSENT || kv.first.empty()) continue;   // (ids.value(id, -2) cannot tell such an id from one that is not listed; no entry has the empty id in the table: see fe_lookup)
+			off.push_back(bytes.size()); len.push_back((uint32_t)kv.first.size()); payload.push_back(kv.second);
+			bytes.insert(bytes.end(), kv.first.begin(), kv.first.end());
+		}
+		has_ids = true;
+		const int64_t k = (int64_t)off.size();
+		if (!k) return;
+		uint64_t cap = 64;
+		while (cap < 2 * (uint64_t)k) cap <<= 1;
+		slot_mask = cap - 1;
+		const char* what = "the table of ids";
+		grow(d_id_bytes, bytes.size() + 1, what, tool); grow(d_id_off, (size_t)k, what, tool); grow(d_id_len, (size_t)k, what, tool); grow(d_id_payload, (size_t)k, what, tool); grow(d_slots, (size_t)cap, what, tool);
+		if (!bytes.empty()) HIPCHK(hipMemcpyAsync(d_id_bytes.p, bytes.data(), bytes.size(), hipMemcpyHostToDevice, stream));
+		HIPCHK(hipMemcpyAsync(d_id_off.p, off.data(), (size_t)k * 8, hipMemcpyHostToDevice, stream)); HIPCHK(hipMemcpyAsync(d_id_len.p, len.data(), (size_t)k * 4, hipMemcpyHostToDevice, stream));
+		HIPCHK(hipMemcpyAsync(d_id_payload.p, payload.data(), (size_t)k * 4, hipMemcpyHostToDevice, stream));
+		HIPCHK(hipMemsetAsync(d_slots.p, 0xff, (size_t)cap * 16, stream));
+		hipLaunchKernelGGL(ngsqc::fe_insert_kernel, dim3(grid_for(k)), dim3(256), 0, stream, d_id_off.p, d_id_len.p, k, d_id_bytes.p, name_hash_mask(sw.name_hash_bits), slot_mask, (unsigned long long*)d_slots.p); KCHECK();
+		HIPCHK(hipStreamSynchronize(stream));   // (the host vectors go)
+	}
+	void outputs(const char* o1, const char* o2, int level)
+	{
+		if (has_out || st.entries) throw ArgError("ngsqc_fqedit_outputs: the outputs are set once, before the first feed");
+		if (!o1) throw ArgError("ngsqc_fqedit_outputs: out1 is needed");
+		if ((sides == 2) != (o2 != nullptr)) throw ArgError(sides == 2 ? "ngsqc_fqedit_outputs: out2 is needed" : "ngsqc_fqedit_outputs: this operation has one output");
+		if (level < 0 || level > 9) throw ArgError("compression level " + std::to_string(level) + " is not in 0..9");
+		const char* paths[2] = {o1, o2};
+		const int64_t W = write_window_bytes(sw.write_window_pieces);
+		for (int k = 0; k < sides; ++k)
+		{
+			out_path[k] = paths[k];
+			out[k].reset(new BgzfStream(tool, W, level));
+			out[k]->sink.open(paths[k], std::string("Could not open file '") + paths[k] + "' for writing!");
+		}
+		has_out = true;
+	}
+	static size_t strip_empty_lines(const uint8_t* t, size_t n)
+	{
+		for (;;)
+		{
+			if (n >= 1 && t[n - 1] == '\n' && (n == 1 || t[n - 2] == '\n')) { n -= 1; continue; }
+			if (n >= 2 && t[n - 1] == '\n' && t[n - 2] == '\r' && (n == 2 || t[n - 3] == '\n')) { n -= 2; continue; }
+			return n;
+		}
+	}
+	// the reference's message for the entry the device named (FastqFileStream.cpp:3-44), from the host's copy of the text
+	void build_error(unsigned long long word)
+	{
+		const uint64_t entry = word >> 8, r = entry - (uint64_t)st.entries; const int kind = (int)(word & 255);
+		const Side& s = side[0];
+		const uint64_t j0 = 4 * r, j1 = std::min<uint64_t>(j0 + 4, s.L);
+		std::vector<uint32_t> lo((size_t)(j1 > j0 ? j1 - j0 : 0) + 1);
+		HIPCHK(hipMemcpyAsync(lo.data(), s.d_lines.p + j0, lo.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, stream)); HIPCHK(hipStreamSynchronize(stream));
+		std::string ln[4];
+		for (size_t k = 0; k + 1 < lo.size() && k < 4; ++k)
+		{
+			size_t b = lo[k], e = lo[k + 1] - 1;
+			if (e > b && s.text[e - 1] == '\r') --e;
+			ln[k].assign((const char*)s.text.data() + b, e - b);
+		}
+		const std::string &header = ln[0], &bases = ln[1], &header2 = ln[2], &quals = ln[3];
+		std::string m = "Invalid Fastq file entry: ";
+		if (kind == FQ_ERR_HEADER) m += "First header line does not start with '@': '" + header + "'.";
+		else if (kind == FQ_ERR_HEADER2) m += "Second header line does not start with '+': '" + header2 + "'.";
+		else if (kind == FQ_ERR_LENGTH) m += "Differing length of bases (" + std::to_string(bases.size()) + ") and qualities string (" + std::to_string(bases.size()) + ") in sequence '" + header + "'.";   // (both numbers are the bases': :17)
+		else if (kind == FQ_ERR_BASE)
+		{
+			char c = '?'; for (char x : bases) if (fq_base_class((uint8_t)x) == 5u) { c = x; break; }
+			m += std::string("Invalid base '") + c + "' encountered in sequence '" + header + "'.";
+		}
+		else
+		{
+			char c = '?'; for (char x : quals) if (!fq_quality_ok((uint8_t)x, P.long_read)) { c = x; break; }
+			m += std::string("Invalid ") + (P.long_read ? "nanopore " : "") + "quality character '" + c + "' with value '" + std::to_string((int)(signed char)c) + "' encountered in sequence '" + header + "'.";
+		}
+		err = m; failed = true; st.err_entry = (int64_t)entry; st.err_kind = kind;
+	}
+	void index_side(Side& s, size_t n_idx)
+	{
+		s.n_idx = n_idx; s.blocks = (int64_t)((n_idx + FQ_BLOCK - 1) / FQ_BLOCK);
+		s.d_text.ensure_slack((size_t)std::max<int64_t>(s.blocks, 1) * FQ_BLOCK); s.d_cnt.ensure_slack((size_t)s.blocks + 1); s.d_base.ensure_slack((size_t)s.blocks + 2);
+		s.d_tmp.ensure_slack(scan_tmp_bytes(s.blocks) + 64); s.d_lines.ensure_slack(n_idx + 2);
+		if (n_idx) HIPCHK(hipMemcpyAsync(s.d_text.p, s.text.data(), n_idx, hipMemcpyHostToDevice, stream));
+	}
+	double ev_ms(int a, int b) { float ms = 0; HIPCHK(hipEventElapsedTime(&ms, ev[a], ev[b])); return ms; }
+	FeArgs args(int64_t n) const
+	{
+		FeArgs a{};
+		for (int k = 0; k < sides; ++k) a.s[k] = FeSide{side[k].d_text.p, side[k].d_lines.p, side[k].L};
+		a.sides = sides; a.n = n; a.entry_base = (unsigned long long)st.entries; a.P = P; a.plan = d_plan.p; a.err = d_err.p;
+		a.t = FeTable{d_slots.p, slot_mask, name_hash_mask(sw.name_hash_bits), d_id_bytes.p, d_id_off.p, d_id_len.p, d_id_payload.p};
+		return a;
+	}
+	int feed(const uint8_t* t1, int64_t n1, const uint8_t* t2, int64_t n2, int last)
+	{
+		if (n1 < 0 || n2 < 0 || (n1 && !t1) || (n2 && !t2)) throw ArgError("ngsqc_fqedit_feed: invalid text");
+		if (sides == 1 && n2) throw ArgError("ngsqc_fqedit_feed: this operation has one input");
+		if (finished) throw ArgError("ngsqc_fqedit_feed: the outputs are closed");
+		if (failed) return NGSQC_E_FORMAT;
+		HIPCHK(hipSetDevice(device));
+		const uint8_t* tx[2] = {t1, t2}; const int64_t nn[2] = {n1, n2};
+		bool any_newline = false;
+		for (int k = 0; k < sides; ++k)
+		{
+			if (side[k].text.size() + (size_t)nn[k] + 1 >= ((size_t)1 << 31)) throw ArgError("ngsqc_fqedit_feed: a piece and the carry in front of it must stay below 2 GiB");
+			if (nn[k]) { any_newline |= memchr(tx[k], '\n', (size_t)nn[k]) != nullptr; side[k].text.insert(side[k].text.end(), tx[k], tx[k] + nn[k]); }
+		}
+		if (!last && !any_newline) return NGSQC_OK;   // no line ends in these pieces: nothing new can be complete
+		HIPCHK(hipEventRecord(ev[0], stream));
+		for (int k = 0; k < sides; ++k)
+		{
+			Side& s = side[k];
+			if (last && !s.text.empty() && s.text.back() != '\n') s.text.push_back('\n');   // a file need not end with a newline
+			const size_t n_idx = strip_empty_lines(s.text.data(), s.text.size());               // empty lines at the end wait in the carry; behind the last piece they are dropped
+			if (last) s.text.resize(n_idx);
+			index_side(s, n_idx);
+		}
+		HIPCHK(hipEventRecord(ev[1], stream));
+		for (int k = 0; k < sides; ++k) { Side& s = side[k]; ngsqc::launch_fastq_line_index(s.d_text.p, s.n_idx, s.d_cnt.p, s.d_base.p, s.d_tmp.p, s.d_lines.p, stream); }
+		HIPCHK(hipEventRecord(ev[2], stream));
+		int64_t tot[2] = {0, 0};
+		for (int k = 0; k < sides; ++k) HIPCHK(hipMemcpyAsync(&tot[k], side[k].d_base.p + side[k].blocks, 8, hipMemcpyDeviceToHost, stream));
+		const double w0 = wall_ms();
+		HIPCHK(hipStreamSynchronize(stream));
+		st.wait_ms += wall_ms() - w0;
+		for (int k = 0; k < sides; ++k) { side[k].L = (unsigned long long)tot[k]; side[k].E = last ? (side[k].L + 3) / 4 : side[k].L / 4; }
+		const int64_t n = (int64_t)(sides == 2 ? std::min(side[0].E, side[1].E) : side[0].E);
+		st.h2d_ms += ev_ms(0, 1); st.index_ms += ev_ms(1, 2);
+		if (n)
+		{
+			d_plan.ensure_slack((size_t)n * FE_PLAN * sides);
+			const FeArgs a = args(n);
+			HIPCHK(hipEventRecord(ev[2], stream));
+			if (P.op != FE_OP_EXTRACT) { hipLaunchKernelGGL(ngsqc::fe_plan_kernel, dim3(grid_for(n)), dim3(256), 0, stream, a); KCHECK(); }
+			else if (P.long_read) { hipLaunchKernelGGL(ngsqc::fe_extract_kernel<64>, dim3(grid_for(n, 4)), dim3(256), 0, stream, a); KCHECK(); }
+			else { hipLaunchKernelGGL(ngsqc::fe_extract_kernel<1>, dim3(grid_for(n)), dim3(256), 0, stream, a); KCHECK(); }
+			HIPCHK(hipEventRecord(ev[3], stream));
+			unsigned long long e_word = FQ_NO_ERROR;
+			HIPCHK(hipMemcpyAsync(&e_word, d_err.p, 8, hipMemcpyDeviceToHost, stream));
+			if (!has_out)
+			{
+				const size_t at = all_plan.size();
+				all_plan.resize(at + (size_t)n * FE_PLAN * sides);
+				HIPCHK(hipMemcpyAsync(all_plan.data() + at, d_plan.p, (size_t)n * FE_PLAN * sides * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+			}
+			const double w1 = wall_ms();
+			HIPCHK(hipStreamSynchronize(stream));
+			st.wait_ms += wall_ms() - w1;
+			st.plan_ms += ev_ms(2, 3);
+			if (e_word != FQ_NO_ERROR) { build_error(e_word); return NGSQC_E_FORMAT; }
+			write_out(a);
+			st.entries += n;
+		}
+		// the carry: what lies behind the last entry on either side; behind the last piece the longer side's surplus is left alone (main.cpp:48 of FastqExtractUMI)
+		for (int k = 0; k < sides; ++k)
+		{
+			Side& s = side[k];
+			size_t from = s.n_idx;
+			if (!last && 4ull * (unsigned long long)n <= s.L)
+			{
+				uint32_t at = 0;
+				HIPCHK(hipMemcpyAsync(&at, s.d_lines.p + 4 * n, sizeof(uint32_t), hipMemcpyDeviceToHost, stream)); HIPCHK(hipStreamSynchronize(stream));
+				from = at;
+			}
+			if (last) s.text.clear(); else s.text.erase(s.text.begin(), s.text.begin() + (ptrdiff_t)std::min(from, s.text.size()));
+		}
+		return NGSQC_OK;
+	}
+	void write_out(const FeArgs& a)
+	{
+		const int64_t n = a.n;
+		for (int k = 0; k < sides; ++k) { grow(d_sz[k], (size_t)n + 1, "the FASTQ entries", tool); grow(d_off[k], (size_t)n + 1, "the FASTQ entries", tool); }
+		grow(d_scan_tmp, scan_tmp_bytes((size_t)n, stream) + 16, "the FASTQ entries", tool);
+		HIPCHK(hipEventRecord(ev[4], stream));
+		hipLaunchKernelGGL(ngsqc::fe_sizes_kernel, dim3(grid_for(n)), dim3(256), 0, stream, a, d_sz[0].p, d_sz[1].p, d_counts.p); KCHECK();
+		if (!has_out) return;
+		for (int k = 0; k < sides; ++k) out[k]->place(d_scan_tmp, d_sz[k].p, d_off[k].p, n, stream);
+		HIPCHK(hipEventRecord(ev[5], stream));
+		HIPCHK(hipStreamSynchronize(stream));
+		st.format_ms += ev_ms(4, 5);   // the sizes and the positions; the format kernels themselves are timed window by window below
+		double z0 = 0, z1 = 0;
+		for (int k = 0; k < sides; ++k)
+		{
+			z0 += out[k]->ms_deflate + out[k]->ms_copy;
+			out[k]->emit(out[k]->placed_end(n), stream, device, [&](const Win& win, int64_t ws) {
+				fmt_clock->mark();
+				hipLaunchKernelGGL(ngsqc::fe_format_kernel, dim3(grid_for(n, 4)), dim3(256), 0, stream, a, k, d_sz[k].p, d_off[k].p, ws, win); KCHECK();
+				fmt_clock->mark();
+			});
+			HIPCHK(hipStreamSynchronize(stream));
+			z1 += out[k]->ms_deflate + out[k]->ms_copy;
+		}
+		st.deflate_ms += z1 - z0;
+		st.format_ms += fmt_clock->total(); fmt_clock.reset(new StageClock(true, stream));
+	}
+	void finish_outputs()
+	{
+		if (finished) return;
+		finished = true;
+		HIPCHK(hipSetDevice(device));
+		for (int k = 0; k < sides; ++k)
+		{
+			if (!out[k]) continue;
+			out[k]->finish(stream, device);
+			if (!out[k]->sink.err.empty()) throw IoError("Could not write to file '" + out_path[k] + "'!");
+		}
+	}
+	void result(ngsqc_fqedit_stats* o)
+	{
+		HIPCHK(hipSetDevice(device));
+		if (!failed) finish_outputs();
+		unsigned long long c[4] = {0, 0, 0, 0};
+		HIPCHK(hipMemcpyAsync(c, d_counts.p, sizeof(c), hipMemcpyDeviceToHost, stream)); HIPCHK(hipStreamSynchronize(stream));
+		for (int k = 0; k < 2; ++k) { st.written[k] = (int64_t)c[k]; st.bytes[k] = (int64_t)c[2 + k]; }
+		if (o) *o = st;
+	}
+};
+
+namespace {
+thread_local std::string g_fqedit_error;
+template <typename F> int fe_guard(ngsqc_fqedit* e, F&& body)
+{
+	std::string& err = e ? e->err : g_fqedit_error;
+	try { return body(); }
+	catch (FormatError& x) { err = x.what(); return NGSQC_E_FORMAT; }
+	catch (ArgError& x) { err = x.what(); return NGSQC_E_ARG; }
+	catch (IoError& x) { err = x.what(); return NGSQC_E_IO; }
+	catch (std::exception& x) { err = x.what(); return NGSQC_E_DEVICE; }
+}
+} // namespace
+
+extern "C" {
+int ngsqc_fqedit_create(int32_t device, const ngsqc_fqedit_params* params, ngsqc_fqedit** out)
+{
+	if (!out) return NGSQC_E_ARG;
+	*out = nullptr;
+	return fe_guard(nullptr, [&] { std::unique_ptr<ngsqc_fqedit> e(new ngsqc_fqedit); e->init(device, params); *out = e.release(); return NGSQC_OK; });
+}
+void ngsqc_fqedit_destroy(ngsqc_fqedit* e) { delete e; }
+const char* ngsqc_fqedit_last_error(const ngsqc_fqedit* e) { return e ? e->err.c_str() : g_fqedit_error.c_str(); }
+int ngsqc_fqedit_ids(ngsqc_fqedit* e, const void* names, const int32_t* name_len, const int32_t* lengths, int64_t n)
+{
+	if (!e) return NGSQC_E_ARG;
+	return fe_guard(e, [&] { e->ids((const uint8_t*)names, name_len, lengths, n); return NGSQC_OK; });
+}
+int ngsqc_fqedit_outputs(ngsqc_fqedit* e, const char* out1, const char* out2, int32_t compression_level)
+{
+	if (!e) return NGSQC_E_ARG;
+	return fe_guard(e, [&] { e->outputs(out1, out2, compression_level); return NGSQC_OK; });
+}
+int ngsqc_fqedit_feed(ngsqc_fqedit* e, const uint8_t* text1, int64_t n1, const uint8_t* text2, int64_t n2, int32_t last)
+{
+	if (!e) return NGSQC_E_ARG;
+	return fe_guard(e, [&] { return e->feed(text1, n1, text2, n2, last); });
+}
+int ngsqc_fqedit_result(ngsqc_fqedit* e, ngsqc_fqedit_stats* st)
+{
+	if (!e) return NGSQC_E_ARG;
+	return fe_guard(e, [&] { e->result(st); return e->failed ? NGSQC_E_FORMAT : NGSQC_OK; });
+}
+int ngsqc_fqedit_plan(ngsqc_fqedit* e, int64_t first, int64_t n, int32_t* out)
+{
+	if (!e) return NGSQC_E_ARG;
+	return fe_guard(e, [&] {
+		if (e->has_out) throw ArgError("ngsqc_fqedit_plan: the plan is kept only when no outputs are set");
+		const int64_t w = (int64_t)FE_PLAN * e->sides;
+		if (first < 0 || n < 0 || (n && !out) || (uint64_t)(first + n) * (uint64_t)w > e->all_plan.size()) throw ArgError("ngsqc_fqedit_plan: entries out of range");
+		std::copy(e->all_plan.begin() + first * w, e->all_plan.begin() + (first + n) * w, out);
+		return NGSQC_OK; });
+}
+}

@@ -1,0 +1,149 @@
+"""The per-entry text of the FASTQ tools (ngs-bits_amd/csrc/fqedit_visit.h - what the GPU library compiles into the kernels of csrc/fqedit.hip) on the CPU,
+against the Python model (tests/fqedit_oracle.py): the plan and the output text on the designed entries (tests/fqedit_cases.py) and on the reference's inputs,
+the first failing entry of FastqExtract's validation, the entries of a feed that is not the last, and the same text as a stand-alone program under
+AddressSanitizer and UBSan."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import fqedit_cases as K
+import fqedit_oracle as M
+from conftest import ROOT
+from test_cpu_fastqtools import REF_TESTS, ids_of, inputs, ref_run
+from test_cpu_seqpurge_emul import prepared
+
+EMUL = os.path.join(ROOT, "tests", "emul")
+CSRC = os.path.join(ROOT, "ngs-bits_amd", "csrc")
+NO_ERROR = (1 << 64) - 1
+OPS = {"trim": 0, "extract": 1, "umi": 2, "convert": 3}
+
+
+@pytest.fixture(scope="module")
+def lib():
+    so = os.path.join(EMUL, "libfqedit.so")
+    srcs = [os.path.join(EMUL, "fqedit_emul.cpp"), os.path.join(CSRC, "fqedit_visit.h"), os.path.join(CSRC, "fastq_visit.h")]
+    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
+        subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-Wall", "-Wno-unknown-pragmas", "-Wno-unused-function", "-o", so, srcs[0]])
+    L = C.CDLL(so)
+    L.fqedit_emul.restype = C.c_int32
+    L.fqedit_emul.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_char_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]
+    L.fqedit_format.restype = C.c_int64
+    L.fqedit_format.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64]
+    return L
+
+
+def int_params(op, kw):
+    return np.array([OPS[op], int(kw.get("long_read", False)), kw.get("start", 0), kw.get("end", 0), kw.get("len", 0), kw.get("max_len", 0), kw.get("cut1", 0), kw.get("cut2", 0),
+                     int(kw.get("invert", False))], np.int32)
+
+
+def id_arrays(ids):
+    names, lengths = ids if ids is not None else ([], None)
+    nl = np.array([len(n) for n in names] + [0], np.int32)
+    pl = np.array([(-1 if lengths is None or lengths[k] is None else lengths[k]) for k in range(len(names))] + [0], np.int32)
+    return b"".join(names), nl, pl, len(names)
+
+
+def emulate(L, op, kw, text1, text2=None, ids=None, last=True, outputs=True):
+    sides = 2 if op == "umi" else 1
+    t = [np.frombuffer(prepared(x, last), np.uint8).copy() for x in ((text1, text2) if sides == 2 else (text1,))] + [np.zeros(0, np.uint8)]
+    cap = max(len(x) for x in t) // 4 + 2
+    plan, out, ip = np.zeros((cap, sides, 8), np.int32), np.zeros(4, np.uint64), int_params(op, kw)
+    blob, nl, pl, n_ids = id_arrays(ids)
+    rc = L.fqedit_emul(t[0].ctypes.data, len(t[0]), t[1].ctypes.data, len(t[1]), sides, int(last), ip.ctypes.data, blob, nl.ctypes.data, pl.ctypes.data, n_ids, plan.ctypes.data, cap, out.ctypes.data)
+    assert rc == 0
+    n = int(out[0])
+    err = None if int(out[1]) == NO_ERROR else (int(out[1]) >> 8, int(out[1]) & 255)
+    texts = []
+    if outputs and err is None:
+        buf = np.zeros(2 * (len(t[0]) + len(t[1])) + 64 * n + 64, np.uint8)
+        for k in range(sides):
+            got = L.fqedit_format(t[0].ctypes.data, len(t[0]), t[1].ctypes.data, len(t[1]), sides, ip.ctypes.data, plan.ctypes.data, n, k, buf.ctypes.data, len(buf))
+            assert got >= 0
+            texts.append(buf[:got].tobytes())
+    return dict(plan=plan[:n] if sides == 2 else plan[:n, 0], err=err, out=texts, carry=(int(out[2]), int(out[3])))
+
+
+def same_as_model(got, r):
+    assert got["err"] is None and r.error is None
+    assert got["plan"].shape == r.plan.shape and np.array_equal(got["plan"], r.plan), np.nonzero((got["plan"] != r.plan).any(axis=tuple(range(1, r.plan.ndim))))[0][:5]
+    assert got["out"] == r.out
+
+
+@pytest.mark.parametrize("variant", ["plain", "crlf", "no final newline"])
+def test_catalogue(lib, variant):
+    for g in K.catalogue():
+        t1, t2 = g.texts(crlf=variant == "crlf", final_newline=variant != "no final newline")
+        same_as_model(emulate(lib, g.op, g.kw, t1, t2, g.ids), g.model())
+
+
+@pytest.mark.parametrize("name", sorted(REF_TESTS))
+def test_reference_inputs(lib, name):
+    t = inputs(name)
+    same_as_model(emulate(lib, REF_TESTS[name][1], REF_TESTS[name][6], t[0], t[1] if len(t) > 1 else None, ids_of(name)), ref_run(name))
+
+
+def test_big_entry(lib):
+    es, t = K.big()
+    for op, kw, ids in (("trim", dict(long_read=True, start=7, end=9, len=69000), None), ("extract", dict(long_read=True), ([b"big", b"s3", b"t59"], [69999, None, 7])), ("convert", dict(), None)):
+        same_as_model(emulate(lib, op, kw, t, None, ids), M.run(op, t, None, ids=ids, **kw))
+
+
+def test_errors(lib):
+    for name, text, long_read, kind, entry, msg in K.error_cases():
+        assert emulate(lib, "extract", dict(long_read=long_read), text, outputs=False)["err"] == (entry, kind), name
+        r = M.run("extract", text, ids=([], None), long_read=long_read)
+        assert (r.error.entry, r.error.kind) == (entry, kind) and msg in str(r.error), name
+
+
+def test_the_entries_of_a_feed_are_those_complete_on_every_side(lib):
+    g = K.by_name("umi-cuts")
+    t1, t2 = g.texts()
+    n = len(g.entries)
+    at1, at2 = (t.rindex(b"\n@f\n") + 1 for t in (t1, t2))   # (a quality line may hold '@': the header is looked for as a whole line)
+    cut2 = at2 + 1                                  # side 2 stops inside its last header
+    got = emulate(lib, g.op, g.kw, t1, t2[:cut2], last=False, outputs=False)
+    assert len(got["plan"]) == n - 1
+    assert got["carry"] == (at1, at2)
+    assert np.array_equal(got["plan"], g.model().plan[:n - 1])
+    g = K.by_name("trim-thresholds")
+    t1, _ = g.texts()
+    got = emulate(lib, g.op, g.kw, t1[:-1], last=False, outputs=False)   # the last line is not ended: its entry waits
+    assert len(got["plan"]) == len(g.entries) - 1 and got["carry"][0] == t1.rindex(b"\n@max_len+1\n") + 1
+
+
+def test_stand_alone_under_sanitizers(tmp_path):
+    """the same text as a program of its own, built with AddressSanitizer and UBSan, over every group of the catalogue, the big entry and the designed errors:
+    the texts lie in heap buffers of exactly their size and every output text in a buffer of exactly the size the plan announces, so a read outside a line or a
+    write behind an entry ends the run; its plan equals the model's"""
+    exe = str(tmp_path / "fqedit_emul_main")
+    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wno-unknown-pragmas", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-o", exe, os.path.join(EMUL, "fqedit_emul_main.cpp")])
+
+    def run(op, kw, t1, t2, ids):
+        (tmp_path / "t1").write_bytes(prepared(t1, True))
+        if t2 is not None:
+            (tmp_path / "t2").write_bytes(prepared(t2, True))
+        if ids is not None:
+            blob, nl, pl, n = id_arrays(ids)
+            (tmp_path / "ids").write_bytes(b"".join(b"%s\t%d\n" % (ids[0][k], pl[k]) for k in range(n)))
+        p = subprocess.run([exe, str(tmp_path / "t1"), str(tmp_path / "t2") if t2 is not None else "-", str(tmp_path / "ids") if ids is not None else "-"] + [str(int(v)) for v in int_params(op, kw)],
+                           capture_output=True, text=True)
+        assert p.returncode == 0, p.stderr[-2000:]
+        return p.stdout.splitlines()
+
+    def check(op, kw, t1, t2, ids, tag):
+        r = M.run(op, t1, t2, ids=ids, **kw)
+        lines = run(op, kw, t1, t2, ids)
+        rows = r.plan.reshape(-1, 8).tolist()
+        assert [[int(v) for v in l.split()] for l in lines[:len(rows)]] == rows, tag
+        assert lines[len(rows):] == ["stream %d: %d bytes" % (k, len(r.out[k])) for k in range(len(r.out))], tag
+    for g in K.catalogue():
+        t1, t2 = g.texts()
+        check(g.op, g.kw, t1, t2, g.ids, g.name)
+    _, t = K.big()
+    check("extract", dict(long_read=True), t, None, ([b"big"], [69999]), "big")
+    for name, text, long_read, kind, entry, _ in K.error_cases():
+        assert run("extract", dict(long_read=long_read), text, None, None)[-1] == "error %d %d" % (entry, kind), name
