@@ -6,7 +6,8 @@
 //   entries     fq_entry_kernel: ONE WAVE PER ENTRY, lanes striding over the cycles as reads_kernel does; validation (fastq_visit.h) leaves the first failing
 //               (entry, kind) in one word by atomicMin.
 // The accumulator (ngsqc_fastq) takes the text in pieces cut anywhere, keeps the incomplete tail as a carry in front of the next piece, and copies through two
-// pinned slots: the kernels of a piece run while the caller inflates the next one (a piece is finished when the next feed, or the result, asks for it).
+// pinned slots: the kernels of a piece run while the caller inflates the next one (a piece is finished when the next feed, or the result, asks for it). Where
+// the text ends, the lines of an entry on the host and the reference's messages are fastq_text.h's, shared with the accumulators of fastq_feed.h.
 #include "handle.h"
 #include "fastq_visit.h"
 #include <map>
@@ -186,6 +187,7 @@ __global__ __launch_bounds__(256) void fq_entry_kernel(const FqKernelArgs a)
 } // namespace ngsqc
 
 // ---------------------------------------------------------------- the accumulator behind the C ABI
+#include "fastq_feed.h"
 using namespace ngsqc::lib;
 
 struct ngsqc_fastq
@@ -231,48 +233,14 @@ struct ngsqc_fastq
 		if (keep_to > keep_from) memcpy(nw.p + keep_from, slot[s].p + keep_from, keep_to - keep_from);
 		std::swap(nw.p, slot[s].p); std::swap(nw.n, slot[s].n);
 	}
-	// the end of the text once the empty lines at its end ("" or "\r") are taken off
-	static size_t strip_empty_lines(const uint8_t* t, size_t n)
-	{
-		for (;;)
-		{
-			if (n >= 1 && t[n - 1] == '\n' && (n == 1 || t[n - 2] == '\n')) { n -= 1; continue; }
-			if (n >= 2 && t[n - 1] == '\n' && t[n - 2] == '\r' && (n == 2 || t[n - 3] == '\n')) { n -= 2; continue; }
-			return n;
-		}
-	}
-	std::string line_text(const uint8_t* t, const std::vector<uint32_t>& lo, size_t j) const
-	{
-		if (j + 1 >= lo.size()) return "";
-		size_t b = lo[j], e = lo[j + 1] - 1;
-		if (e > b && t[e - 1] == '\r') --e;
-		return std::string((const char*)t + b, e - b);
-	}
-	// the reference's message for the entry the device named (FastqFileStream.cpp:3-44); the text of the piece is still in its slot
+	// the reference's message for the entry the device named (FastqFileStream.cpp:3-44; kind 6 is ours); the text of the piece is still in its slot
 	void build_error(unsigned long long word, uint64_t n_lines)
 	{
 		const uint64_t entry = word >> 8, r = entry - entry_base; const int kind = (int)(word & 255);
-		const uint64_t j0 = 4 * r, j1 = std::min<uint64_t>(j0 + 4, n_lines);
-		std::vector<uint32_t> lo((size_t)(j1 - j0) + 1);
-		HIPCHK(hipMemcpyAsync(lo.data(), d_lines.p + j0, lo.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, stream)); HIPCHK(hipStreamSynchronize(stream));
-		const uint8_t* t = slot[cur].p;
-		const std::string header = line_text(t, lo, 0), bases = line_text(t, lo, 1), header2 = line_text(t, lo, 2), quals = line_text(t, lo, 3);
-		std::string m = "Invalid Fastq file entry: ";
-		if (kind == FQ_ERR_HEADER) m += "First header line does not start with '@': '" + header + "'.";
-		else if (kind == FQ_ERR_HEADER2) m += "Second header line does not start with '+': '" + header2 + "'.";
-		else if (kind == FQ_ERR_LENGTH) m += "Differing length of bases (" + std::to_string(bases.size()) + ") and qualities string (" + std::to_string(bases.size()) + ") in sequence '" + header + "'.";   // (both numbers are the bases': :17)
-		else if (kind == FQ_ERR_BASE)
-		{
-			char c = '?'; for (char x : bases) if (fq_base_class((uint8_t)x) == 5u) { c = x; break; }
-			m += std::string("Invalid base '") + c + "' encountered in sequence '" + header + "'.";
-		}
-		else if (kind == FQ_ERR_QUALITY)
-		{
-			char c = '?'; for (char x : quals) if (!fq_quality_ok((uint8_t)x, long_read)) { c = x; break; }
-			m += std::string("Invalid ") + (long_read ? "nanopore " : "") + "quality character '" + c + "' with value '" + std::to_string((int)(signed char)c) + "' encountered in sequence '" + header + "'.";
-		}
-		else m += "Entry " + std::to_string(entry) + " has an empty header line and bases or qualities that cannot be counted (" + std::to_string(bases.size()) + " bases, " + std::to_string(quals.size()) + " qualities).";
-		err = m; failed = true;
+		std::string ln[4]; fq_fetch_entry(slot[cur].p, d_lines.p, n_lines, r, stream, ln);
+		if (kind != FQ_ERR_EMPTY_HEADER) err = fq_validate_message(kind, ln, long_read);
+		else err = "Invalid Fastq file entry: Entry " + std::to_string(entry) + " has an empty header line and bases or qualities that cannot be counted (" + std::to_string(ln[1].size()) + " bases, " + std::to_string(ln[3].size()) + " qualities).";
+		failed = true;
 		rep.err_file = file_ordinal; rep.err_entry = (int64_t)entry; rep.err_kind = kind;
 	}
 	// waits for the piece in flight and takes its results
@@ -350,9 +318,9 @@ struct ngsqc_fastq
 		if (last)
 		{
 			if (len && t[len - 1] != '\n') t[len++] = '\n';   // a file need not end with a newline
-			len = n_idx = strip_empty_lines(t, len);           // lines at the end of a file that are all empty are ignored
+			len = n_idx = fq_strip_empty_lines(t, len);        // lines at the end of a file that are all empty are ignored
 		}
-		else n_idx = strip_empty_lines(t, len);              // ... and they may still turn out to be that: they wait in the carry
+		else n_idx = fq_strip_empty_lines(t, len);           // ... and they may still turn out to be that: they wait in the carry
 		launch(n_idx, last != 0, direction);
 		if (last) { finish(); if (failed) return NGSQC_E_FORMAT; }
 		return NGSQC_OK;
@@ -385,41 +353,31 @@ struct ngsqc_fastq
 	}
 };
 
-namespace {
-thread_local std::string g_fastq_error;
-template <typename F> int fq_guard(ngsqc_fastq* f, F&& body)
-{
-	std::string& err = f ? f->err : g_fastq_error;
-	try { return body(); }
-	catch (FormatError& e) { err = e.what(); return NGSQC_E_FORMAT; }
-	catch (ArgError& e) { err = e.what(); return NGSQC_E_ARG; }
-	catch (std::exception& e) { err = e.what(); return NGSQC_E_DEVICE; }
-}
-} // namespace
+namespace { thread_local std::string g_fastq_error; }
 
 extern "C" {
 int ngsqc_fastq_create(int32_t device, int32_t long_read, ngsqc_fastq** out)
 {
 	if (!out) return NGSQC_E_ARG;
 	*out = nullptr;
-	return fq_guard(nullptr, [&] { std::unique_ptr<ngsqc_fastq> f(new ngsqc_fastq); f->init(device, long_read); *out = f.release(); return NGSQC_OK; });
+	return fastq_guard((ngsqc_fastq*)nullptr, g_fastq_error, [&] { std::unique_ptr<ngsqc_fastq> f(new ngsqc_fastq); f->init(device, long_read); *out = f.release(); return NGSQC_OK; });
 }
 void ngsqc_fastq_destroy(ngsqc_fastq* f) { delete f; }
 const char* ngsqc_fastq_last_error(const ngsqc_fastq* f) { return f ? f->err.c_str() : g_fastq_error.c_str(); }
 int ngsqc_fastq_feed(ngsqc_fastq* f, const uint8_t* text, int64_t n, int32_t direction, int32_t last)
 {
 	if (!f) return NGSQC_E_ARG;
-	return fq_guard(f, [&] { return f->feed(text, n, direction, last); });
+	return fastq_guard(f, g_fastq_error, [&] { return f->feed(text, n, direction, last); });
 }
 int ngsqc_fastq_result(ngsqc_fastq* f, ngsqc_read_stats* st, ngsqc_fastq_report* rep)
 {
 	if (!f) return NGSQC_E_ARG;
-	return fq_guard(f, [&] { f->result(st, rep); return f->failed ? NGSQC_E_FORMAT : NGSQC_OK; });
+	return fastq_guard(f, g_fastq_error, [&] { f->result(st, rep); return f->failed ? NGSQC_E_FORMAT : NGSQC_OK; });
 }
 int ngsqc_fastq_length_hist(ngsqc_fastq* f, int64_t* out, int64_t cap)
 {
 	if (!f) return NGSQC_E_ARG;
-	return fq_guard(f, [&] {
+	return fastq_guard(f, g_fastq_error, [&] {
 		if (f->res_len.empty()) throw ArgError("no read statistics: call ngsqc_fastq_result first");
 		if (!out || cap < (int64_t)f->res_len.size()) throw ArgError("read-length buffer too small");
 		std::copy(f->res_len.begin(), f->res_len.end(), out);
@@ -428,7 +386,7 @@ int ngsqc_fastq_length_hist(ngsqc_fastq* f, int64_t* out, int64_t cap)
 int ngsqc_fastq_cycle_stats(ngsqc_fastq* f, int64_t* out, int64_t n_cycles)
 {
 	if (!f) return NGSQC_E_ARG;
-	return fq_guard(f, [&] {
+	return fastq_guard(f, g_fastq_error, [&] {
 		if (f->res_cyc.empty()) throw ArgError("no read statistics: call ngsqc_fastq_result first");
 		if (!out || n_cycles < 0) throw ArgError("invalid cycle buffer");
 		const int64_t n = std::min<int64_t>(n_cycles, RQ_CYC);

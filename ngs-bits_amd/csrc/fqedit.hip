@@ -11,7 +11,7 @@
 //   format      fe_sizes_kernel (the bytes an entry gives its stream; the counters of the statistics) -> BgzfStream::place -> fe_format_kernel: one wave per
 //               entry writes the bytes of the entry that fall inside the stream's window (fe_entry_byte); the windows are deflated on the device.
 // The accumulator (ngsqc_fqedit) takes the texts in pieces cut anywhere, as ngsqc_purge does: the entries of a feed are those complete on every side, the rest
-// waits as the side's carry.
+// waits as the side's carry. Both do it through FastqFeed (fastq_feed.h) and write through FastqOutputs (fastq_outputs.h); the reference's messages are fastq_text.h's.
 #include "join.h"
 #include "fqedit_visit.h"
 #include <unordered_map>
@@ -150,37 +150,23 @@ __global__ __launch_bounds__(256) void fe_format_kernel(const FeArgs a, int k, c
 } // namespace ngsqc
 
 // ---------------------------------------------------------------- the accumulator behind the C ABI
+#include "fastq_feed.h"
+#include "fastq_outputs.h"
 using namespace ngsqc::lib;
 
 struct ngsqc_fqedit
 {
-	int device = 0; hipStream_t stream = nullptr; std::string err; bool failed = false;
+	std::string err; bool failed = false;
 	FeParams P{}; int sides = 1; const char* tool = "FastqTrim"; CallSwitches sw;
-	struct Side
-	{
-		std::vector<uint8_t> text;   // the carry, then what was fed
-		size_t n_idx = 0; int64_t blocks = 0; unsigned long long L = 0, E = 0;
-		DevBuf<uint8_t> d_text, d_tmp; DevBuf<uint32_t> d_cnt, d_lines; DevBuf<int64_t> d_base;
-	} side[2];
+	FastqFeed in;   // (in front of out: fastq_outputs.h)
+	std::unique_ptr<Timer> plan_clock;
 	// the id table
 	DevBuf<uint8_t> d_id_bytes; DevBuf<uint64_t> d_id_off; DevBuf<uint32_t> d_id_len; DevBuf<int32_t> d_id_payload; DevBuf<ulonglong2> d_slots; uint64_t slot_mask = 0; bool has_ids = false;
 	DevBuf<int32_t> d_plan; DevBuf<unsigned long long> d_err, d_counts;
-	DevBuf<uint64_t> d_sz[2], d_off[2]; DevBuf<uint8_t> d_scan_tmp;
-	std::unique_ptr<BgzfStream> out[2]; std::string out_path[2]; bool has_out = false, finished = false;
+	FastqOutputs out;
 	std::vector<int32_t> all_plan;
 	ngsqc_fqedit_stats st{};
-	hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-	std::unique_ptr<StageClock> fmt_clock;
 
-	~ngsqc_fqedit()
-	{
-		(void)hipSetDevice(device);
-		if (stream) (void)hipStreamSynchronize(stream);
-		for (auto& o : out) o.reset();
-		fmt_clock.reset();
-		if (stream) (void)hipStreamDestroy(stream);
-		for (auto& e : ev) if (e) (void)hipEventDestroy(e);
-	}
 	void init(int dev, const ngsqc_fqedit_params* p)
 	{
 		if (!p) throw ArgError("ngsqc_fqedit_create: no parameters");
@@ -190,24 +176,18 @@ struct ngsqc_fqedit
 		if (p->cut1 < 0 || p->cut2 < 0) throw ArgError("cut1 and cut2 must not be negative!");
 		P.op = p->op; P.long_read = p->long_read ? 1 : 0; P.start = p->start; P.end = p->end; P.len = p->len; P.max_len = p->max_len; P.cut1 = p->cut1; P.cut2 = p->cut2; P.invert = p->invert ? 1 : 0;
 		sides = P.op == FE_OP_UMI ? 2 : 1; tool = names[P.op];
-		int n_dev = 0;
-		if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) throw std::runtime_error("no HIP device available (libngsqc_hip has no CPU fallback)");
-		if (dev < 0 || dev >= n_dev) throw ArgError("no such device");
-		device = dev; st.err_entry = -1;
-		HIPCHK(hipSetDevice(device));
-		HIPCHK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-		for (auto& e : ev) HIPCHK(hipEventCreate(&e));
-		fmt_clock.reset(new StageClock(true, stream));
+		in.open(dev, sides); st.err_entry = -1;
+		plan_clock.reset(new Timer(in.stream)); out.init(tool, sides, in.device, in.stream);
 		d_err.alloc(1); d_counts.alloc(4);
-		HIPCHK(hipMemsetAsync(d_err.p, 0xff, 8, stream)); HIPCHK(hipMemsetAsync(d_counts.p, 0, 4 * 8, stream));
-		HIPCHK(hipStreamSynchronize(stream));
+		HIPCHK(hipMemsetAsync(d_err.p, 0xff, 8, in.stream)); HIPCHK(hipMemsetAsync(d_counts.p, 0, 4 * 8, in.stream));
+		HIPCHK(hipStreamSynchronize(in.stream));
 	}
 	void ids(const uint8_t* names, const int32_t* name_len, const int32_t* lengths, int64_t n)
 	{
 		if (P.op != FE_OP_EXTRACT) throw ArgError("ngsqc_fqedit_ids: only FastqExtract takes ids");
 		if (has_ids || st.entries) throw ArgError("ngsqc_fqedit_ids: the ids are set once, before the first feed");
 		if (n < 0 || (n && (!names || !name_len))) throw ArgError("ngsqc_fqedit_ids: invalid ids");
-		HIPCHK(hipSetDevice(device));
+		HIPCHK(hipSetDevice(in.device));
 		// QHash::insert (main.cpp:51): a later duplicate replaces the earlier one
 		std::unordered_map<std::string, int32_t> m;
 		uint64_t o = 0;
@@ -232,82 +212,33 @@ struct ngsqc_fqedit
 		slot_mask = cap - 1;
 		const char* what = "the table of ids";
 		grow(d_id_bytes, bytes.size() + 1, what, tool); grow(d_id_off, (size_t)k, what, tool); grow(d_id_len, (size_t)k, what, tool); grow(d_id_payload, (size_t)k, what, tool); grow(d_slots, (size_t)cap, what, tool);
-		if (!bytes.empty()) HIPCHK(hipMemcpyAsync(d_id_bytes.p, bytes.data(), bytes.size(), hipMemcpyHostToDevice, stream));
-		HIPCHK(hipMemcpyAsync(d_id_off.p, off.data(), (size_t)k * 8, hipMemcpyHostToDevice, stream)); HIPCHK(hipMemcpyAsync(d_id_len.p, len.data(), (size_t)k * 4, hipMemcpyHostToDevice, stream));
-		HIPCHK(hipMemcpyAsync(d_id_payload.p, payload.data(), (size_t)k * 4, hipMemcpyHostToDevice, stream));
-		HIPCHK(hipMemsetAsync(d_slots.p, 0xff, (size_t)cap * 16, stream));
-		hipLaunchKernelGGL(ngsqc::fe_insert_kernel, dim3(grid_for(k)), dim3(256), 0, stream, d_id_off.p, d_id_len.p, k, d_id_bytes.p, name_hash_mask(sw.name_hash_bits), slot_mask, (unsigned long long*)d_slots.p); KCHECK();
-		HIPCHK(hipStreamSynchronize(stream));   // (the host vectors go)
+		if (!bytes.empty()) HIPCHK(hipMemcpyAsync(d_id_bytes.p, bytes.data(), bytes.size(), hipMemcpyHostToDevice, in.stream));
+		HIPCHK(hipMemcpyAsync(d_id_off.p, off.data(), (size_t)k * 8, hipMemcpyHostToDevice, in.stream)); HIPCHK(hipMemcpyAsync(d_id_len.p, len.data(), (size_t)k * 4, hipMemcpyHostToDevice, in.stream));
+		HIPCHK(hipMemcpyAsync(d_id_payload.p, payload.data(), (size_t)k * 4, hipMemcpyHostToDevice, in.stream));
+		HIPCHK(hipMemsetAsync(d_slots.p, 0xff, (size_t)cap * 16, in.stream));
+		hipLaunchKernelGGL(ngsqc::fe_insert_kernel, dim3(grid_for(k)), dim3(256), 0, in.stream, d_id_off.p, d_id_len.p, k, d_id_bytes.p, name_hash_mask(sw.name_hash_bits), slot_mask, (unsigned long long*)d_slots.p); KCHECK();
+		HIPCHK(hipStreamSynchronize(in.stream));   // (the host vectors go)
 	}
 	void outputs(const char* o1, const char* o2, int level)
 	{
-		if (has_out || st.entries) throw ArgError("ngsqc_fqedit_outputs: the outputs are set once, before the first feed");
+		if (out.opened || st.entries) throw ArgError("ngsqc_fqedit_outputs: the outputs are set once, before the first feed");
 		if (!o1) throw ArgError("ngsqc_fqedit_outputs: out1 is needed");
 		if ((sides == 2) != (o2 != nullptr)) throw ArgError(sides == 2 ? "ngsqc_fqedit_outputs: out2 is needed" : "ngsqc_fqedit_outputs: this operation has one output");
 		if (level < 0 || level > 9) throw ArgError("compression level " + std::to_string(level) + " is not in 0..9");
-		const char* paths[2] = {o1, o2};
-		const int64_t W = write_window_bytes(sw.write_window_pieces);
-		for (int k = 0; k < sides; ++k)
-		{
-			out_path[k] = paths[k];
-			out[k].reset(new BgzfStream(tool, W, level));
-			out[k]->sink.open(paths[k], std::string("Could not open file '") + paths[k] + "' for writing!");
-		}
-		has_out = true;
-	}
-	static size_t strip_empty_lines(const uint8_t* t, size_t n)
-	{
-		for (;;)
-		{
-			if (n >= 1 && t[n - 1] == '\n' && (n == 1 || t[n - 2] == '\n')) { n -= 1; continue; }
-			if (n >= 2 && t[n - 1] == '\n' && t[n - 2] == '\r' && (n == 2 || t[n - 3] == '\n')) { n -= 2; continue; }
-			return n;
-		}
+		const char* paths[4] = {o1, o2, nullptr, nullptr};
+		out.open(paths, write_window_bytes(sw.write_window_pieces), level);
 	}
 	// the reference's message for the entry the device named (FastqFileStream.cpp:3-44), from the host's copy of the text
 	void build_error(unsigned long long word)
 	{
 		const uint64_t entry = word >> 8, r = entry - (uint64_t)st.entries; const int kind = (int)(word & 255);
-		const Side& s = side[0];
-		const uint64_t j0 = 4 * r, j1 = std::min<uint64_t>(j0 + 4, s.L);
-		std::vector<uint32_t> lo((size_t)(j1 > j0 ? j1 - j0 : 0) + 1);
-		HIPCHK(hipMemcpyAsync(lo.data(), s.d_lines.p + j0, lo.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, stream)); HIPCHK(hipStreamSynchronize(stream));
-		std::string ln[4];
-		for (size_t k = 0; k + 1 < lo.size() && k < 4; ++k)
-		{
-			size_t b = lo[k], e = lo[k + 1] - 1;
-			if (e > b && s.text[e - 1] == '\r') --e;
-			ln[k].assign((const char*)s.text.data() + b, e - b);
-		}
-		const std::string &header = ln[0], &bases = ln[1], &header2 = ln[2], &quals = ln[3];
-		std::string m = "Invalid Fastq file entry: ";
-		if (kind == FQ_ERR_HEADER) m += "First header line does not start with '@': '" + header + "'.";
-		else if (kind == FQ_ERR_HEADER2) m += "Second header line does not start with '+': '" + header2 + "'.";
-		else if (kind == FQ_ERR_LENGTH) m += "Differing length of bases (" + std::to_string(bases.size()) + ") and qualities string (" + std::to_string(bases.size()) + ") in sequence '" + header + "'.";   // (both numbers are the bases': :17)
-		else if (kind == FQ_ERR_BASE)
-		{
-			char c = '?'; for (char x : bases) if (fq_base_class((uint8_t)x) == 5u) { c = x; break; }
-			m += std::string("Invalid base '") + c + "' encountered in sequence '" + header + "'.";
-		}
-		else
-		{
-			char c = '?'; for (char x : quals) if (!fq_quality_ok((uint8_t)x, P.long_read)) { c = x; break; }
-			m += std::string("Invalid ") + (P.long_read ? "nanopore " : "") + "quality character '" + c + "' with value '" + std::to_string((int)(signed char)c) + "' encountered in sequence '" + header + "'.";
-		}
-		err = m; failed = true; st.err_entry = (int64_t)entry; st.err_kind = kind;
+		std::string ln[4]; in.entry_lines(0, r, ln);
+		err = fq_validate_message(kind, ln, P.long_read); failed = true; st.err_entry = (int64_t)entry; st.err_kind = kind;
 	}
-	void index_side(Side& s, size_t n_idx)
-	{
-		s.n_idx = n_idx; s.blocks = (int64_t)((n_idx + FQ_BLOCK - 1) / FQ_BLOCK);
-		s.d_text.ensure_slack((size_t)std::max<int64_t>(s.blocks, 1) * FQ_BLOCK); s.d_cnt.ensure_slack((size_t)s.blocks + 1); s.d_base.ensure_slack((size_t)s.blocks + 2);
-		s.d_tmp.ensure_slack(scan_tmp_bytes(s.blocks) + 64); s.d_lines.ensure_slack(n_idx + 2);
-		if (n_idx) HIPCHK(hipMemcpyAsync(s.d_text.p, s.text.data(), n_idx, hipMemcpyHostToDevice, stream));
-	}
-	double ev_ms(int a, int b) { float ms = 0; HIPCHK(hipEventElapsedTime(&ms, ev[a], ev[b])); return ms; }
 	FeArgs args(int64_t n) const
 	{
 		FeArgs a{};
-		for (int k = 0; k < sides; ++k) a.s[k] = FeSide{side[k].d_text.p, side[k].d_lines.p, side[k].L};
+		for (int k = 0; k < sides; ++k) a.s[k] = FeSide{in.side[k].d_text.p, in.side[k].d_lines.p, in.side[k].L};
 		a.sides = sides; a.n = n; a.entry_base = (unsigned long long)st.entries; a.P = P; a.plan = d_plan.p; a.err = d_err.p;
 		a.t = FeTable{d_slots.p, slot_mask, name_hash_mask(sw.name_hash_bits), d_id_bytes.p, d_id_off.p, d_id_len.p, d_id_payload.p};
 		return a;
@@ -316,49 +247,25 @@ struct ngsqc_fqedit
 	{
 		if (n1 < 0 || n2 < 0 || (n1 && !t1) || (n2 && !t2)) throw ArgError("ngsqc_fqedit_feed: invalid text");
 		if (sides == 1 && n2) throw ArgError("ngsqc_fqedit_feed: this operation has one input");
-		if (finished) throw ArgError("ngsqc_fqedit_feed: the outputs are closed");
+		if (out.finished) throw ArgError("ngsqc_fqedit_feed: the outputs are closed");
 		if (failed) return NGSQC_E_FORMAT;
-		HIPCHK(hipSetDevice(device));
+		HIPCHK(hipSetDevice(in.device));
 		const uint8_t* tx[2] = {t1, t2}; const int64_t nn[2] = {n1, n2};
-		bool any_newline = false;
-		for (int k = 0; k < sides; ++k)
-		{
-			if (side[k].text.size() + (size_t)nn[k] + 1 >= ((size_t)1 << 31)) throw ArgError("ngsqc_fqedit_feed: a piece and the carry in front of it must stay below 2 GiB");
-			if (nn[k]) { any_newline |= memchr(tx[k], '\n', (size_t)nn[k]) != nullptr; side[k].text.insert(side[k].text.end(), tx[k], tx[k] + nn[k]); }
-		}
-		if (!last && !any_newline) return NGSQC_OK;   // no line ends in these pieces: nothing new can be complete
-		HIPCHK(hipEventRecord(ev[0], stream));
-		for (int k = 0; k < sides; ++k)
-		{
-			Side& s = side[k];
-			if (last && !s.text.empty() && s.text.back() != '\n') s.text.push_back('\n');   // a file need not end with a newline
-			const size_t n_idx = strip_empty_lines(s.text.data(), s.text.size());               // empty lines at the end wait in the carry; behind the last piece they are dropped
-			if (last) s.text.resize(n_idx);
-			index_side(s, n_idx);
-		}
-		HIPCHK(hipEventRecord(ev[1], stream));
-		for (int k = 0; k < sides; ++k) { Side& s = side[k]; ngsqc::launch_fastq_line_index(s.d_text.p, s.n_idx, s.d_cnt.p, s.d_base.p, s.d_tmp.p, s.d_lines.p, stream); }
-		HIPCHK(hipEventRecord(ev[2], stream));
-		int64_t tot[2] = {0, 0};
-		for (int k = 0; k < sides; ++k) HIPCHK(hipMemcpyAsync(&tot[k], side[k].d_base.p + side[k].blocks, 8, hipMemcpyDeviceToHost, stream));
-		const double w0 = wall_ms();
-		HIPCHK(hipStreamSynchronize(stream));
-		st.wait_ms += wall_ms() - w0;
-		for (int k = 0; k < sides; ++k) { side[k].L = (unsigned long long)tot[k]; side[k].E = last ? (side[k].L + 3) / 4 : side[k].L / 4; }
-		const int64_t n = (int64_t)(sides == 2 ? std::min(side[0].E, side[1].E) : side[0].E);
-		st.h2d_ms += ev_ms(0, 1); st.index_ms += ev_ms(1, 2);
+		const int64_t n = in.feed("ngsqc_fqedit_feed", tx, nn, last != 0, st.h2d_ms, st.index_ms, st.wait_ms);
+		if (n < 0) return NGSQC_OK;
+		hipStream_t stream = in.stream;
 		if (n)
 		{
 			d_plan.ensure_slack((size_t)n * FE_PLAN * sides);
 			const FeArgs a = args(n);
-			HIPCHK(hipEventRecord(ev[2], stream));
+			plan_clock->start();
 			if (P.op != FE_OP_EXTRACT) { hipLaunchKernelGGL(ngsqc::fe_plan_kernel, dim3(grid_for(n)), dim3(256), 0, stream, a); KCHECK(); }
 			else if (P.long_read) { hipLaunchKernelGGL(ngsqc::fe_extract_kernel<64>, dim3(grid_for(n, 4)), dim3(256), 0, stream, a); KCHECK(); }
 			else { hipLaunchKernelGGL(ngsqc::fe_extract_kernel<1>, dim3(grid_for(n)), dim3(256), 0, stream, a); KCHECK(); }
-			HIPCHK(hipEventRecord(ev[3], stream));
+			plan_clock->mark();
 			unsigned long long e_word = FQ_NO_ERROR;
 			HIPCHK(hipMemcpyAsync(&e_word, d_err.p, 8, hipMemcpyDeviceToHost, stream));
-			if (!has_out)
+			if (!out.opened)
 			{
 				const size_t at = all_plan.size();
 				all_plan.resize(at + (size_t)n * FE_PLAN * sides);
@@ -367,123 +274,72 @@ struct ngsqc_fqedit
 			const double w1 = wall_ms();
 			HIPCHK(hipStreamSynchronize(stream));
 			st.wait_ms += wall_ms() - w1;
-			st.plan_ms += ev_ms(2, 3);
+			st.plan_ms += plan_clock->elapsed();
 			if (e_word != FQ_NO_ERROR) { build_error(e_word); return NGSQC_E_FORMAT; }
 			write_out(a);
 			st.entries += n;
 		}
 		// the carry: what lies behind the last entry on either side; behind the last piece the longer side's surplus is left alone (main.cpp:48 of FastqExtractUMI)
-		for (int k = 0; k < sides; ++k)
-		{
-			Side& s = side[k];
-			size_t from = s.n_idx;
-			if (!last && 4ull * (unsigned long long)n <= s.L)
-			{
-				uint32_t at = 0;
-				HIPCHK(hipMemcpyAsync(&at, s.d_lines.p + 4 * n, sizeof(uint32_t), hipMemcpyDeviceToHost, stream)); HIPCHK(hipStreamSynchronize(stream));
-				from = at;
-			}
-			if (last) s.text.clear(); else s.text.erase(s.text.begin(), s.text.begin() + (ptrdiff_t)std::min(from, s.text.size()));
-		}
+		in.cut_carry(n, last != 0);
 		return NGSQC_OK;
 	}
 	void write_out(const FeArgs& a)
 	{
 		const int64_t n = a.n;
-		for (int k = 0; k < sides; ++k) { grow(d_sz[k], (size_t)n + 1, "the FASTQ entries", tool); grow(d_off[k], (size_t)n + 1, "the FASTQ entries", tool); }
-		grow(d_scan_tmp, scan_tmp_bytes((size_t)n, stream) + 16, "the FASTQ entries", tool);
-		HIPCHK(hipEventRecord(ev[4], stream));
-		hipLaunchKernelGGL(ngsqc::fe_sizes_kernel, dim3(grid_for(n)), dim3(256), 0, stream, a, d_sz[0].p, d_sz[1].p, d_counts.p); KCHECK();
-		if (!has_out) return;
-		for (int k = 0; k < sides; ++k) out[k]->place(d_scan_tmp, d_sz[k].p, d_off[k].p, n, stream);
-		HIPCHK(hipEventRecord(ev[5], stream));
-		HIPCHK(hipStreamSynchronize(stream));
-		st.format_ms += ev_ms(4, 5);   // the sizes and the positions; the format kernels themselves are timed window by window below
-		double z0 = 0, z1 = 0;
-		for (int k = 0; k < sides; ++k)
-		{
-			z0 += out[k]->ms_deflate + out[k]->ms_copy;
-			out[k]->emit(out[k]->placed_end(n), stream, device, [&](const Win& win, int64_t ws) {
-				fmt_clock->mark();
-				hipLaunchKernelGGL(ngsqc::fe_format_kernel, dim3(grid_for(n, 4)), dim3(256), 0, stream, a, k, d_sz[k].p, d_off[k].p, ws, win); KCHECK();
-				fmt_clock->mark();
-			});
-			HIPCHK(hipStreamSynchronize(stream));
-			z1 += out[k]->ms_deflate + out[k]->ms_copy;
-		}
-		st.deflate_ms += z1 - z0;
-		st.format_ms += fmt_clock->total(); fmt_clock.reset(new StageClock(true, stream));
-	}
-	void finish_outputs()
-	{
-		if (finished) return;
-		finished = true;
-		HIPCHK(hipSetDevice(device));
-		for (int k = 0; k < sides; ++k)
-		{
-			if (!out[k]) continue;
-			out[k]->finish(stream, device);
-			if (!out[k]->sink.err.empty()) throw IoError("Could not write to file '" + out_path[k] + "'!");
-		}
+		out.begin(n);
+		hipLaunchKernelGGL(ngsqc::fe_sizes_kernel, dim3(grid_for(n)), dim3(256), 0, in.stream, a, out.d_sz[0].p, out.d_sz[1].p, d_counts.p); KCHECK();
+		if (!out.opened) return;
+		out.write(n, st.format_ms, st.deflate_ms, [&](int k, const Win& win, int64_t ws) {
+			hipLaunchKernelGGL(ngsqc::fe_format_kernel, dim3(grid_for(n, 4)), dim3(256), 0, in.stream, a, k, out.d_sz[k].p, out.d_off[k].p, ws, win); KCHECK();
+		});
 	}
 	void result(ngsqc_fqedit_stats* o)
 	{
-		HIPCHK(hipSetDevice(device));
-		if (!failed) finish_outputs();
+		HIPCHK(hipSetDevice(in.device));
+		if (!failed) out.finish();
 		unsigned long long c[4] = {0, 0, 0, 0};
-		HIPCHK(hipMemcpyAsync(c, d_counts.p, sizeof(c), hipMemcpyDeviceToHost, stream)); HIPCHK(hipStreamSynchronize(stream));
+		HIPCHK(hipMemcpyAsync(c, d_counts.p, sizeof(c), hipMemcpyDeviceToHost, in.stream)); HIPCHK(hipStreamSynchronize(in.stream));
 		for (int k = 0; k < 2; ++k) { st.written[k] = (int64_t)c[k]; st.bytes[k] = (int64_t)c[2 + k]; }
 		if (o) *o = st;
 	}
 };
 
-namespace {
-thread_local std::string g_fqedit_error;
-template <typename F> int fe_guard(ngsqc_fqedit* e, F&& body)
-{
-	std::string& err = e ? e->err : g_fqedit_error;
-	try { return body(); }
-	catch (FormatError& x) { err = x.what(); return NGSQC_E_FORMAT; }
-	catch (ArgError& x) { err = x.what(); return NGSQC_E_ARG; }
-	catch (IoError& x) { err = x.what(); return NGSQC_E_IO; }
-	catch (std::exception& x) { err = x.what(); return NGSQC_E_DEVICE; }
-}
-} // namespace
+namespace { thread_local std::string g_fqedit_error; }
 
 extern "C" {
 int ngsqc_fqedit_create(int32_t device, const ngsqc_fqedit_params* params, ngsqc_fqedit** out)
 {
 	if (!out) return NGSQC_E_ARG;
 	*out = nullptr;
-	return fe_guard(nullptr, [&] { std::unique_ptr<ngsqc_fqedit> e(new ngsqc_fqedit); e->init(device, params); *out = e.release(); return NGSQC_OK; });
+	return fastq_guard((ngsqc_fqedit*)nullptr, g_fqedit_error, [&] { std::unique_ptr<ngsqc_fqedit> e(new ngsqc_fqedit); e->init(device, params); *out = e.release(); return NGSQC_OK; });
 }
 void ngsqc_fqedit_destroy(ngsqc_fqedit* e) { delete e; }
 const char* ngsqc_fqedit_last_error(const ngsqc_fqedit* e) { return e ? e->err.c_str() : g_fqedit_error.c_str(); }
 int ngsqc_fqedit_ids(ngsqc_fqedit* e, const void* names, const int32_t* name_len, const int32_t* lengths, int64_t n)
 {
 	if (!e) return NGSQC_E_ARG;
-	return fe_guard(e, [&] { e->ids((const uint8_t*)names, name_len, lengths, n); return NGSQC_OK; });
+	return fastq_guard(e, g_fqedit_error, [&] { e->ids((const uint8_t*)names, name_len, lengths, n); return NGSQC_OK; });
 }
 int ngsqc_fqedit_outputs(ngsqc_fqedit* e, const char* out1, const char* out2, int32_t compression_level)
 {
 	if (!e) return NGSQC_E_ARG;
-	return fe_guard(e, [&] { e->outputs(out1, out2, compression_level); return NGSQC_OK; });
+	return fastq_guard(e, g_fqedit_error, [&] { e->outputs(out1, out2, compression_level); return NGSQC_OK; });
 }
 int ngsqc_fqedit_feed(ngsqc_fqedit* e, const uint8_t* text1, int64_t n1, const uint8_t* text2, int64_t n2, int32_t last)
 {
 	if (!e) return NGSQC_E_ARG;
-	return fe_guard(e, [&] { return e->feed(text1, n1, text2, n2, last); });
+	return fastq_guard(e, g_fqedit_error, [&] { return e->feed(text1, n1, text2, n2, last); });
 }
 int ngsqc_fqedit_result(ngsqc_fqedit* e, ngsqc_fqedit_stats* st)
 {
 	if (!e) return NGSQC_E_ARG;
-	return fe_guard(e, [&] { e->result(st); return e->failed ? NGSQC_E_FORMAT : NGSQC_OK; });
+	return fastq_guard(e, g_fqedit_error, [&] { e->result(st); return e->failed ? NGSQC_E_FORMAT : NGSQC_OK; });
 }
 int ngsqc_fqedit_plan(ngsqc_fqedit* e, int64_t first, int64_t n, int32_t* out)
 {
 	if (!e) return NGSQC_E_ARG;
-	return fe_guard(e, [&] {
-		if (e->has_out) throw ArgError("ngsqc_fqedit_plan: the plan is kept only when no outputs are set");
+	return fastq_guard(e, g_fqedit_error, [&] {
+		if (e->out.opened) throw ArgError("ngsqc_fqedit_plan: the plan is kept only when no outputs are set");
 		const int64_t w = (int64_t)FE_PLAN * e->sides;
 		if (first < 0 || n < 0 || (n && !out) || (uint64_t)(first + n) * (uint64_t)w > e->all_plan.size()) throw ArgError("ngsqc_fqedit_plan: entries out of range");
 		std::copy(e->all_plan.begin() + first * w, e->all_plan.begin() + (first + n) * w, out);

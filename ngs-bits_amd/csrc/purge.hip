@@ -9,7 +9,8 @@
 //   format      pg_sizes_kernel (the bytes a pair gives each of the four output streams, from the plan) -> BgzfStream::place -> pg_format_kernel: one wave
 //               per entry writes its four lines, truncated to the plan's length, into the stream's window; the windows are deflated on the device.
 // The accumulator (ngsqc_purge) takes the two texts in pieces cut anywhere; the pairs of a feed are the entries complete on both sides, the rest of either
-// side waits as its carry. The counters of TrimmingStatistics are summed on the host from the plan, bases_perc_trim_sum in pair order as doubles.
+// side waits as its carry: FastqFeed of fastq_feed.h, as the four output streams are FastqOutputs of fastq_outputs.h. The counters of TrimmingStatistics are
+// summed on the host from the plan, bases_perc_trim_sum in pair order as doubles.
 #include "join.h"
 #include "purge_visit.h"
 
@@ -253,37 +254,22 @@ __global__ __launch_bounds__(256) void pg_format_kernel(const PgOutArgs a, int k
 } // namespace ngsqc
 
 // ---------------------------------------------------------------- the accumulator behind the C ABI
+#include "fastq_feed.h"
+#include "fastq_outputs.h"
 using namespace ngsqc::lib;
 
 struct ngsqc_purge
 {
-	int device = 0; hipStream_t stream = nullptr; std::string err; bool failed = false;
+	std::string err; bool failed = false;
 	PgParams P{}; std::string a1, a2; CallSwitches sw;
 	DevBuf<double> d_tail;
-	struct Side
-	{
-		std::vector<uint8_t> text;   // the carry, then what was fed
-		size_t n_idx = 0; int64_t blocks = 0; unsigned long long L = 0, E = 0; uint32_t carry_at = 0;
-		DevBuf<uint8_t> d_text, d_tmp; DevBuf<uint32_t> d_cnt, d_lines; DevBuf<int64_t> d_base;
-		std::string name;
-	} side[2];
+	FastqFeed in; std::string name[2] = {"in1", "in2"};   // (in front of out: fastq_outputs.h)
+	std::unique_ptr<Timer> plan_clock;
 	DevBuf<int32_t> d_plan; DevBuf<unsigned long long> d_acons, d_ec, d_err;
-	DevBuf<uint64_t> d_sz[4], d_off[4]; DevBuf<uint8_t> d_scan_tmp;
-	std::unique_ptr<BgzfStream> out[4]; std::string out_path[4]; bool has_out = false, out3 = false, finished = false;
+	FastqOutputs out; bool out3 = false;
 	std::vector<int32_t> h_plan, all_plan;
 	ngsqc_purge_stats st{};
-	hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-	std::unique_ptr<StageClock> fmt_clock;
 
-	~ngsqc_purge()
-	{
-		(void)hipSetDevice(device);
-		if (stream) (void)hipStreamSynchronize(stream);
-		for (auto& o : out) o.reset();
-		fmt_clock.reset();
-		if (stream) (void)hipStreamDestroy(stream);
-		for (auto& e : ev) if (e) (void)hipEventDestroy(e);
-	}
 	static void check_adapter(const char* s, const char* which, std::string& dst)
 	{
 		if (!s) throw ArgError(std::string("ngsqc_purge_create: no ") + which + " adapter");
@@ -300,66 +286,28 @@ struct ngsqc_purge
 		memcpy(P.a1, a1.data(), std::min<size_t>(a1.size(), PG_ADAPTER)); memcpy(P.a2, a2.data(), std::min<size_t>(a2.size(), PG_ADAPTER));
 		P.a_size = (int)std::min<size_t>(20, std::min(a1.size(), a2.size()));
 		P.match_perc = p->match_perc; P.mep = p->mep; P.min_len = p->min_len; P.qcut = p->qcut; P.qwin = p->qwin; P.qoff = p->qoff; P.ncut = p->ncut; P.ec = p->ec ? 1 : 0;
-		int n_dev = 0;
-		if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) throw std::runtime_error("no HIP device available (libngsqc_hip has no CPU fallback)");
-		if (dev < 0 || dev >= n_dev) throw ArgError("no such device");
-		device = dev; st.err_pair = -1;
-		side[0].name = "in1"; side[1].name = "in2";
-		HIPCHK(hipSetDevice(device));
-		HIPCHK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-		for (auto& e : ev) HIPCHK(hipEventCreate(&e));
-		fmt_clock.reset(new StageClock(true, stream));
+		in.open(dev, 2); st.err_pair = -1;
+		plan_clock.reset(new Timer(in.stream)); out.init("SeqPurge", 4, in.device, in.stream);
 		std::vector<double> tail((size_t)PG_TAIL_SIZE); pg_build_tail(tail.data());
-		d_tail.upload(tail, stream);
+		d_tail.upload(tail, in.stream);
 		d_acons.alloc(PG_ACONS); d_ec.alloc(PG_EC); d_err.alloc(1);
-		HIPCHK(hipMemsetAsync(d_acons.p, 0, PG_ACONS * 8, stream)); HIPCHK(hipMemsetAsync(d_ec.p, 0, PG_EC * 8, stream)); HIPCHK(hipMemsetAsync(d_err.p, 0xff, 8, stream));
-		HIPCHK(hipStreamSynchronize(stream));
+		HIPCHK(hipMemsetAsync(d_acons.p, 0, PG_ACONS * 8, in.stream)); HIPCHK(hipMemsetAsync(d_ec.p, 0, PG_EC * 8, in.stream)); HIPCHK(hipMemsetAsync(d_err.p, 0xff, 8, in.stream));
+		HIPCHK(hipStreamSynchronize(in.stream));
 	}
 	void outputs(const char* o1, const char* o2, const char* o3a, const char* o3b, int level)
 	{
-		if (has_out || st.pairs) throw ArgError("ngsqc_purge_outputs: the outputs are set once, before the first feed");
+		if (out.opened || st.pairs) throw ArgError("ngsqc_purge_outputs: the outputs are set once, before the first feed");
 		if (!o1 || !o2) throw ArgError("ngsqc_purge_outputs: out1 and out2 are needed");
 		if ((o3a != nullptr) != (o3b != nullptr)) throw ArgError("ngsqc_purge_outputs: out3_r1 and out3_r2 are set together");
 		if (level < 0 || level > 9) throw ArgError("compression level " + std::to_string(level) + " is not in 0..9");
 		const char* paths[4] = {o1, o2, o3a, o3b};
-		const int64_t W = write_window_bytes(sw.write_window_pieces);
-		for (int k = 0; k < 4; ++k)
-		{
-			if (!paths[k]) continue;
-			out_path[k] = paths[k];
-			out[k].reset(new BgzfStream("SeqPurge", W, level));
-			out[k]->sink.open(paths[k], std::string("Could not open file '") + paths[k] + "' for writing!");
-		}
-		has_out = true; out3 = o3a != nullptr;
-	}
-	static size_t strip_empty_lines(const uint8_t* t, size_t n)
-	{
-		for (;;)
-		{
-			if (n >= 1 && t[n - 1] == '\n' && (n == 1 || t[n - 2] == '\n')) { n -= 1; continue; }
-			if (n >= 2 && t[n - 1] == '\n' && t[n - 2] == '\r' && (n == 2 || t[n - 3] == '\n')) { n -= 2; continue; }
-			return n;
-		}
-	}
-	std::string host_line(const Side& s, const std::vector<uint32_t>& lo, size_t j) const
-	{
-		if (j + 1 >= lo.size()) return "";
-		size_t b = lo[j], e = lo[j + 1] - 1;
-		if (e > b && s.text[e - 1] == '\r') --e;
-		return std::string((const char*)s.text.data() + b, e - b);
-	}
-	// the four lines of entry r of a side, from the device's line index and the host's copy of the text
-	void host_entry(Side& s, uint64_t r, std::string ln[4])
-	{
-		const uint64_t j0 = 4 * r, j1 = std::min<uint64_t>(j0 + 4, s.L);
-		std::vector<uint32_t> lo((size_t)(j1 > j0 ? j1 - j0 : 0) + 1);
-		HIPCHK(hipMemcpyAsync(lo.data(), s.d_lines.p + j0, lo.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, stream)); HIPCHK(hipStreamSynchronize(stream));
-		for (int k = 0; k < 4; ++k) ln[k] = host_line(s, lo, (size_t)k);
+		out.open(paths, write_window_bytes(sw.write_window_pieces), level);
+		out3 = o3a != nullptr;
 	}
 	void build_error(unsigned long long word)
 	{
 		const uint64_t pair = word >> 8, r = pair - (uint64_t)st.pairs; const int kind = (int)(word & 255);
-		std::string l1[4], l2[4]; host_entry(side[0], r, l1); host_entry(side[1], r, l2);
+		std::string l1[4], l2[4]; in.entry_lines(0, r, l1); in.entry_lines(1, r, l2);
 		std::string m;
 		if (kind == PG_ERR_LENGTHS)
 		{
@@ -379,14 +327,6 @@ struct ngsqc_purge
 		else m = "Read length unsupported! A maximum read length of " + std::to_string(PG_MAXLEN) + " is supported!";
 		err = m; failed = true; st.err_pair = (int64_t)pair; st.err_kind = kind;
 	}
-	void index_side(Side& s, size_t n_idx)
-	{
-		s.n_idx = n_idx; s.blocks = (int64_t)((n_idx + FQ_BLOCK - 1) / FQ_BLOCK);
-		s.d_text.ensure_slack((size_t)std::max<int64_t>(s.blocks, 1) * FQ_BLOCK); s.d_cnt.ensure_slack((size_t)s.blocks + 1); s.d_base.ensure_slack((size_t)s.blocks + 2);
-		s.d_tmp.ensure_slack(scan_tmp_bytes(s.blocks) + 64); s.d_lines.ensure_slack(n_idx + 2);
-		if (n_idx) HIPCHK(hipMemcpyAsync(s.d_text.p, s.text.data(), n_idx, hipMemcpyHostToDevice, stream));
-	}
-	double ev_ms(int a, int b) { float ms = 0; HIPCHK(hipEventElapsedTime(&ms, ev[a], ev[b])); return ms; }
 	void add_stats(int64_t n)
 	{
 		for (int64_t r = 0; r < n; ++r)
@@ -409,46 +349,22 @@ struct ngsqc_purge
 	int feed(const uint8_t* t1, int64_t n1, const uint8_t* t2, int64_t n2, int last)
 	{
 		if (n1 < 0 || n2 < 0 || (n1 && !t1) || (n2 && !t2)) throw ArgError("ngsqc_purge_feed: invalid text");
-		if (finished) throw ArgError("ngsqc_purge_feed: the outputs are closed");
+		if (out.finished) throw ArgError("ngsqc_purge_feed: the outputs are closed");
 		if (failed) return NGSQC_E_FORMAT;
-		HIPCHK(hipSetDevice(device));
+		HIPCHK(hipSetDevice(in.device));
 		const uint8_t* tx[2] = {t1, t2}; const int64_t nn[2] = {n1, n2};
-		bool any_newline = false;
-		for (int k = 0; k < 2; ++k)
-		{
-			if (side[k].text.size() + (size_t)nn[k] + 1 >= ((size_t)1 << 31)) throw ArgError("ngsqc_purge_feed: a piece and the carry in front of it must stay below 2 GiB");
-			if (nn[k]) { any_newline |= memchr(tx[k], '\n', (size_t)nn[k]) != nullptr; side[k].text.insert(side[k].text.end(), tx[k], tx[k] + nn[k]); }
-		}
-		if (!last && !any_newline) return NGSQC_OK;   // no line ends in these pieces: nothing new can be complete
-		HIPCHK(hipEventRecord(ev[0], stream));
-		for (int k = 0; k < 2; ++k)
-		{
-			Side& s = side[k];
-			if (last && !s.text.empty() && s.text.back() != '\n') s.text.push_back('\n');   // a file need not end with a newline
-			const size_t n_idx = strip_empty_lines(s.text.data(), s.text.size());               // empty lines at the end wait in the carry; behind the last piece they are dropped
-			if (last) s.text.resize(n_idx);
-			index_side(s, n_idx);
-		}
-		HIPCHK(hipEventRecord(ev[1], stream));
-		for (int k = 0; k < 2; ++k) { Side& s = side[k]; launch_fastq_line_index(s.d_text.p, s.n_idx, s.d_cnt.p, s.d_base.p, s.d_tmp.p, s.d_lines.p, stream); }
-		HIPCHK(hipEventRecord(ev[2], stream));
-		int64_t tot[2] = {0, 0};
-		for (int k = 0; k < 2; ++k) HIPCHK(hipMemcpyAsync(&tot[k], side[k].d_base.p + side[k].blocks, 8, hipMemcpyDeviceToHost, stream));
-		const double w0 = wall_ms();
-		HIPCHK(hipStreamSynchronize(stream));
-		st.wait_ms += wall_ms() - w0;
-		for (int k = 0; k < 2; ++k) { side[k].L = (unsigned long long)tot[k]; side[k].E = last ? (side[k].L + 3) / 4 : side[k].L / 4; }
-		const int64_t n = (int64_t)std::min(side[0].E, side[1].E);
-		st.h2d_ms += ev_ms(0, 1); st.index_ms += ev_ms(1, 2);
+		const int64_t n = in.feed("ngsqc_purge_feed", tx, nn, last != 0, st.h2d_ms, st.index_ms, st.wait_ms);
+		if (n < 0) return NGSQC_OK;
+		const FastqFeed::Side* side = in.side; hipStream_t stream = in.stream;
 		if (n)
 		{
 			d_plan.ensure_slack((size_t)n * PG_PLAN);
 			PgArgs a{side[0].d_text.p, side[0].d_lines.p, side[0].L, side[1].d_text.p, side[1].d_lines.p, side[1].L, n, (unsigned long long)st.pairs, P, d_tail.p,
 			         d_plan.p, d_acons.p, d_ec.p, d_err.p};
-			HIPCHK(hipEventRecord(ev[2], stream));
+			plan_clock->start();
 			const int64_t wgs = std::min<int64_t>((n + 3) / 4, 256 * 8);
 			hipLaunchKernelGGL(pg_plan_kernel, dim3((unsigned)wgs), dim3(256), 0, stream, a); KCHECK();
-			HIPCHK(hipEventRecord(ev[3], stream));
+			plan_clock->mark();
 			h_plan.resize((size_t)n * PG_PLAN);
 			unsigned long long e_word = FQ_NO_ERROR;
 			HIPCHK(hipMemcpyAsync(h_plan.data(), d_plan.p, h_plan.size() * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
@@ -456,132 +372,78 @@ struct ngsqc_purge
 			const double w1 = wall_ms();
 			HIPCHK(hipStreamSynchronize(stream));
 			st.wait_ms += wall_ms() - w1;
-			st.plan_ms += ev_ms(2, 3);
+			st.plan_ms += plan_clock->elapsed();
 			if (e_word != FQ_NO_ERROR) { build_error(e_word); return NGSQC_E_FORMAT; }
-			if (has_out) write_out(n);
+			if (out.opened) write_out(n);
 			else all_plan.insert(all_plan.end(), h_plan.begin(), h_plan.end());
 			add_stats(n);
 			st.pairs += n;
 		}
-		// the carry: what lies behind the last pair on either side
+		// the carry: what lies behind the last pair on either side; text left on a side behind the last piece is entries without a mate
+		const int rest = in.cut_carry(n, last != 0);
 		for (int k = 0; k < 2; ++k)
-		{
-			Side& s = side[k];
-			size_t from = s.n_idx;
-			if (4ull * (unsigned long long)n <= s.L)
-			{
-				uint32_t at = 0;
-				HIPCHK(hipMemcpyAsync(&at, s.d_lines.p + 4 * n, sizeof(uint32_t), hipMemcpyDeviceToHost, stream)); HIPCHK(hipStreamSynchronize(stream));
-				from = at;
-			}
-			if (last && from < s.n_idx && !failed)
-			{
-				Side& o = side[k ^ 1];
-				err = "File " + s.name + " has more entries than " + o.name + "!"; failed = true; st.err_pair = st.pairs; st.err_kind = 0;
-			}
-			if (last) s.text.clear(); else s.text.erase(s.text.begin(), s.text.begin() + (ptrdiff_t)std::min(from, s.text.size()));
-		}
+			if (last && (rest >> k & 1) && !failed) { err = "File " + name[k] + " has more entries than " + name[k ^ 1] + "!"; failed = true; st.err_pair = st.pairs; st.err_kind = 0; }
 		return failed ? NGSQC_E_FORMAT : NGSQC_OK;
 	}
 	void write_out(int64_t n)
 	{
+		const FastqFeed::Side* side = in.side;
 		PgOutArgs oa{side[0].d_text.p, side[0].d_lines.p, side[0].L, side[1].d_text.p, side[1].d_lines.p, side[1].L, n, d_plan.p, P.min_len, out3 ? 1 : 0};
-		for (int k = 0; k < 4; ++k) { grow(d_sz[k], (size_t)n + 1, "the FASTQ entries", "SeqPurge"); grow(d_off[k], (size_t)n + 1, "the FASTQ entries", "SeqPurge"); }
-		grow(d_scan_tmp, scan_tmp_bytes((size_t)n, stream) + 16, "the FASTQ entries", "SeqPurge");
-		HIPCHK(hipEventRecord(ev[4], stream));
-		hipLaunchKernelGGL(pg_sizes_kernel, dim3(grid_for(n)), dim3(256), 0, stream, oa, d_sz[0].p, d_sz[1].p, d_sz[2].p, d_sz[3].p); KCHECK();
-		for (int k = 0; k < 4; ++k) if (out[k]) out[k]->place(d_scan_tmp, d_sz[k].p, d_off[k].p, n, stream);
-		HIPCHK(hipEventRecord(ev[5], stream));
-		HIPCHK(hipStreamSynchronize(stream));
-		st.format_ms += ev_ms(4, 5);   // the sizes and the positions; the format kernels themselves are timed window by window below
-		double z0 = 0, z1 = 0;
-		for (int k = 0; k < 4; ++k)
-		{
-			if (!out[k]) continue;
-			z0 += out[k]->ms_deflate + out[k]->ms_copy;
-			out[k]->emit(out[k]->placed_end(n), stream, device, [&](const Win& win, int64_t ws) {
-				fmt_clock->mark();
-				hipLaunchKernelGGL(pg_format_kernel, dim3(grid_for(n, 4)), dim3(256), 0, stream, oa, k, d_sz[k].p, d_off[k].p, ws, win); KCHECK();
-				fmt_clock->mark();
-			});
-			HIPCHK(hipStreamSynchronize(stream));
-			z1 += out[k]->ms_deflate + out[k]->ms_copy;
-		}
-		st.deflate_ms += z1 - z0;
-		st.format_ms += fmt_clock->total(); fmt_clock.reset(new StageClock(true, stream));
-	}
-	void finish_outputs()
-	{
-		if (finished) return;
-		finished = true;
-		HIPCHK(hipSetDevice(device));
-		for (int k = 0; k < 4; ++k)
-		{
-			if (!out[k]) continue;
-			out[k]->finish(stream, device);
-			if (!out[k]->sink.err.empty()) throw IoError("Could not write to file '" + out_path[k] + "'!");
-		}
+		out.begin(n);
+		hipLaunchKernelGGL(pg_sizes_kernel, dim3(grid_for(n)), dim3(256), 0, in.stream, oa, out.d_sz[0].p, out.d_sz[1].p, out.d_sz[2].p, out.d_sz[3].p); KCHECK();
+		out.write(n, st.format_ms, st.deflate_ms, [&](int k, const Win& win, int64_t ws) {
+			hipLaunchKernelGGL(pg_format_kernel, dim3(grid_for(n, 4)), dim3(256), 0, in.stream, oa, k, out.d_sz[k].p, out.d_off[k].p, ws, win); KCHECK();
+		});
 	}
 	void result(ngsqc_purge_stats* o)
 	{
-		HIPCHK(hipSetDevice(device));
-		if (!failed) finish_outputs();
+		HIPCHK(hipSetDevice(in.device));
+		if (!failed) out.finish();
 		std::vector<unsigned long long> ac(PG_ACONS), ec(PG_EC);
-		HIPCHK(hipMemcpyAsync(ac.data(), d_acons.p, ac.size() * 8, hipMemcpyDeviceToHost, stream)); HIPCHK(hipMemcpyAsync(ec.data(), d_ec.p, ec.size() * 8, hipMemcpyDeviceToHost, stream));
-		HIPCHK(hipStreamSynchronize(stream));
+		HIPCHK(hipMemcpyAsync(ac.data(), d_acons.p, ac.size() * 8, hipMemcpyDeviceToHost, in.stream)); HIPCHK(hipMemcpyAsync(ec.data(), d_ec.p, ec.size() * 8, hipMemcpyDeviceToHost, in.stream));
+		HIPCHK(hipStreamSynchronize(in.stream));
 		for (int i = 0; i < PG_ACONS; ++i) st.acons[i] = (int64_t)ac[i];
 		for (int i = 0; i < PG_MAXLEN; ++i) { st.ec_mismatch_r1[i] = (int64_t)ec[i]; st.ec_mismatch_r2[i] = (int64_t)ec[PG_MAXLEN + i]; st.ec_errors_per_read[i] = (int64_t)ec[2 * PG_MAXLEN + i]; }
 		if (o) *o = st;
 	}
 };
 
-namespace {
-thread_local std::string g_purge_error;
-template <typename F> int pg_guard(ngsqc_purge* p, F&& body)
-{
-	std::string& err = p ? p->err : g_purge_error;
-	try { return body(); }
-	catch (FormatError& e) { err = e.what(); return NGSQC_E_FORMAT; }
-	catch (ArgError& e) { err = e.what(); return NGSQC_E_ARG; }
-	catch (IoError& e) { err = e.what(); return NGSQC_E_IO; }
-	catch (std::exception& e) { err = e.what(); return NGSQC_E_DEVICE; }
-}
-} // namespace
+namespace { thread_local std::string g_purge_error; }
 
 extern "C" {
 int ngsqc_purge_create(int32_t device, const ngsqc_purge_params* params, ngsqc_purge** out)
 {
 	if (!out) return NGSQC_E_ARG;
 	*out = nullptr;
-	return pg_guard(nullptr, [&] { std::unique_ptr<ngsqc_purge> p(new ngsqc_purge); p->init(device, params); *out = p.release(); return NGSQC_OK; });
+	return fastq_guard((ngsqc_purge*)nullptr, g_purge_error, [&] { std::unique_ptr<ngsqc_purge> p(new ngsqc_purge); p->init(device, params); *out = p.release(); return NGSQC_OK; });
 }
 void ngsqc_purge_destroy(ngsqc_purge* p) { delete p; }
 const char* ngsqc_purge_last_error(const ngsqc_purge* p) { return p ? p->err.c_str() : g_purge_error.c_str(); }
 int ngsqc_purge_outputs(ngsqc_purge* p, const char* out1, const char* out2, const char* out3_r1, const char* out3_r2, int32_t compression_level)
 {
 	if (!p) return NGSQC_E_ARG;
-	return pg_guard(p, [&] { p->outputs(out1, out2, out3_r1, out3_r2, compression_level); return NGSQC_OK; });
+	return fastq_guard(p, g_purge_error, [&] { p->outputs(out1, out2, out3_r1, out3_r2, compression_level); return NGSQC_OK; });
 }
 int ngsqc_purge_file_names(ngsqc_purge* p, const char* name1, const char* name2)
 {
 	if (!p || !name1 || !name2) return NGSQC_E_ARG;
-	return pg_guard(p, [&] { p->side[0].name = name1; p->side[1].name = name2; return NGSQC_OK; });
+	return fastq_guard(p, g_purge_error, [&] { p->name[0] = name1; p->name[1] = name2; return NGSQC_OK; });
 }
 int ngsqc_purge_feed(ngsqc_purge* p, const uint8_t* text1, int64_t n1, const uint8_t* text2, int64_t n2, int32_t last)
 {
 	if (!p) return NGSQC_E_ARG;
-	return pg_guard(p, [&] { return p->feed(text1, n1, text2, n2, last); });
+	return fastq_guard(p, g_purge_error, [&] { return p->feed(text1, n1, text2, n2, last); });
 }
 int ngsqc_purge_result(ngsqc_purge* p, ngsqc_purge_stats* st)
 {
 	if (!p) return NGSQC_E_ARG;
-	return pg_guard(p, [&] { p->result(st); return p->failed ? NGSQC_E_FORMAT : NGSQC_OK; });
+	return fastq_guard(p, g_purge_error, [&] { p->result(st); return p->failed ? NGSQC_E_FORMAT : NGSQC_OK; });
 }
 int ngsqc_purge_plan(ngsqc_purge* p, int64_t first, int64_t n, int32_t* out)
 {
 	if (!p) return NGSQC_E_ARG;
-	return pg_guard(p, [&] {
-		if (p->has_out) throw ArgError("ngsqc_purge_plan: the plan is kept only when no outputs are set");
+	return fastq_guard(p, g_purge_error, [&] {
+		if (p->out.opened) throw ArgError("ngsqc_purge_plan: the plan is kept only when no outputs are set");
 		if (first < 0 || n < 0 || (n && !out) || (uint64_t)(first + n) * PG_PLAN > p->all_plan.size()) throw ArgError("ngsqc_purge_plan: pairs out of range");
 		std::copy(p->all_plan.begin() + first * PG_PLAN, p->all_plan.begin() + (first + n) * PG_PLAN, out);
 		return NGSQC_OK; });

@@ -1,6 +1,7 @@
 """SeqPurge's per-pair text (ngs-bits_amd/csrc/purge_visit.h - what the GPU library compiles into the kernels of csrc/purge.hip) on the CPU, against the Python
 model (tests/seqpurge_oracle.py): the plan, the output text, the consensus pile-ups and the -ec histograms on the designed pairs (tests/purge_cases.py) and on
-the reference's inputs; the table of the binomial tail against exact integers; and the sweep that allows the kernel to count whole offsets."""
+the reference's inputs; the table of the binomial tail against exact integers; the sweep that allows the kernel to count whole offsets; and the host's view of
+FASTQ text that the three FASTQ accumulators share (csrc/fastq_text.h), as a stand-alone program under the sanitizers."""
 import ctypes as C
 import os
 import subprocess
@@ -8,6 +9,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import fastq_model as F
 import purge_cases as K
 import seqpurge_oracle as M
 from conftest import ROOT
@@ -161,3 +163,64 @@ def test_stand_alone_under_sanitizers(tmp_path):
         assert lines[len(r.plan):] == ["stream %d: %d bytes" % (k, len(r.out[k])) for k in range(4)], g.name
     for name, t1, t2, kind, pair, _ in K.error_cases():
         assert run(t1, t2, M.Params())[-1] == "error %d %d" % (pair, kind), name
+
+
+E = b"@r\nACGT\n+\nIIII\n"
+HOST_TEXTS = [
+    ("lf", E + b"@s\nAC\n+x\nII\n"),
+    ("crlf", E.replace(b"\n", b"\r\n") + b"@s\r\n\r\n+\r\n\r\n"),
+    ("cr inside a line", b"@r\rx\nAC\rGT\n+\nIIIII\n"),
+    ("no final newline", E + b"@s\nAC\n+\nII"),
+    ("no final newline, crlf", b"@s\r\nAC\r\n+\r\nII\r"),
+    ("blank tail", E + b"\n\r\n\n"),
+    ("blank lines inside stay", b"@r\n\n\n\n" + E + b"\r\n"),
+    ("incomplete: 1 line", E + b"@s\n"),
+    ("incomplete: 2 lines", E + b"@s\nAC\n"),
+    ("incomplete: 3 lines", E + b"@s\nAC\n+\n"),
+    ("incomplete: 3 lines, no final newline", E + b"@s\nAC\n+"),
+    ("empty", b""),
+    ("newline alone", b"\n"),
+    ("crlf alone", b"\r\n"),
+    ("kind 1", b"r\nACGT\n+\nIIII\n"),
+    ("kind 2", b"@r\nACGT\n-\nIIII\n"),
+    ("kind 3", b"@r\nACGT\n+\nIII\n"),
+    ("kind 4", E + b"@r\nACxT\n+\nIIII\n"),
+    ("kind 5", b"@r\nACGT\n+\nII~I\n"),
+    ("kind 5, a byte above 127", b"@r\nACGT\n+\nI\xffII\n"),
+    ("kind 6", b"\nACGT\n+\nIII\n" + E),
+]
+
+
+@pytest.mark.parametrize("long_read", [0, 1])
+def test_host_text_stand_alone_under_sanitizers(tmp_path, long_read):
+    """csrc/fastq_text.h - where the accumulators end a text, how they cut an entry's lines out of their copy of it with the offsets fetched from the device, and
+    the reference's messages - as a program of its own under AddressSanitizer and UBSan: the text and the line offsets lie in heap buffers of exactly their size.
+    The stripped length against parse_fastq's rule (and against prepared(), for a text in the middle of a file too), the lines against parse_fastq, the kinds
+    and messages against the model of FastqEntry::validate."""
+    exe = str(tmp_path / "fastq_text_main")
+    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-o", exe,
+                           os.path.join(EMUL, "fastq_text_main.cpp")])
+    for i, (_, t) in enumerate(HOST_TEXTS):
+        (tmp_path / ("t%d" % i)).write_bytes(t)
+    p = subprocess.run([exe, str(long_read)] + [str(tmp_path / ("t%d" % i)) for i in range(len(HOST_TEXTS))], capture_output=True, text=True)
+    assert p.returncode == 0, p.stderr[-2000:]
+    out = iter(p.stdout.splitlines())
+    kinds = set()
+    for name, t in HOST_TEXTS:
+        entries = M.parse_fastq(t)
+        flat = [l for e in entries for l in e]
+        while flat and flat[-1] == b"":
+            flat.pop()                                       # (the lines parse_fastq supplied for an incomplete last entry)
+        whole = t if t.endswith(b"\n") or not t else t + b"\n"
+        ends = [j + 1 for j, c in enumerate(whole) if c == 10]
+        stripped = ends[len(flat) - 1] if flat else 0        # behind the newline of the last line that is kept
+        assert next(out).split() == ["text", str(len(prepared(t, False))), str(stripped), str(len(flat))], name
+        assert stripped == len(prepared(t, True)), name
+        for r, e in enumerate(entries):
+            kind = F.validate(e, bool(long_read))
+            kinds.add(kind)
+            assert next(out).split() == ["entry", str(r), str(kind)], name
+            assert tuple(bytes.fromhex(next(out)) for _ in range(4)) == e, name
+            assert bytes.fromhex(next(out)) == (F.message(e, kind, bool(long_read)).encode("latin-1") if 1 <= kind <= 5 else b""), name
+    assert next(out, None) is None
+    assert kinds == set(range(7))
