@@ -165,7 +165,8 @@ typedef struct ngsqc_indel_window {
 #define NGSQC_W_DEPTH        2   /* reads with start <= window.start and end >= window.end, minus one per N operation spanning the window */
 #define NGSQC_W_INS          3   /* I operations of those reads at a genome position in [start, end], one per operation */
 #define NGSQC_W_DEL          4   /* D operations ... */
-#define NGSQC_W_MATCH        5   /* ... equal to the query allele: "+SEQ" / "-REF" */
+#define NGSQC_W_MATCH        5   /* ... equal to the query allele: "+SEQ" / "-REF" (a deletion running past the reference's end, the length of the BAM
+                                    header, is compared by the bases in front of the end, as FastaFileIndex::seq returns them) */
 #define NGSQC_INDEL_NCOUNTERS 6
 /* A read that the reference would walk (it spans the window and holds an I, D or N operation) and that holds an operation the reference throws on gives
  * NGSQC_E_FORMAT "Unknown CIGAR operation". */

@@ -166,7 +166,7 @@ void launch_pileup_long(const uint8_t* infl, const int64_t* recoff, const int64_
 
 // indel windows (indel.hip: BamReader::getIndels for a table of windows; counts = u32[n_windows][8], see there). start: 1-based window starts, sorted per
 // reference; win: the rest of each window; pool: query alleles and reference slices; buckets as in the site pileup; tid_maxlen: longest window of a reference
-struct IndelWin { int32_t end, kind, len, pad; int64_t qoff, soff; };
+struct IndelWin { int32_t end, kind, len, ref_len; int64_t qoff, soff; };   // ref_len: length of the window's reference (where FastaFileIndex::seq cuts a deletion)
 struct IndelTables
 {
 	const int32_t* start; const IndelWin* win; const uint8_t* pool;

@@ -8,7 +8,8 @@
 //   2 depth          records with start <= window.start and end >= window.end, minus one for each N operation that spans the window (:1068-1075); kept
 //                    modulo 2^32 (a decrement is + 0xFFFFFFFF): the host reads it as int32
 //   3 n_ins, 4 n_del I / D operations of spanning records whose genome position lies in [start, end] (:1046-1066), one per operation
-//   5 n_match        ... equal to the window's query allele: "+SEQ" (the read's bases, mid() semantics) / "-REF" (the reference slice at the operation)
+//   5 n_match        ... equal to the window's query allele: "+SEQ" (the read's bases, mid() semantics) / "-REF" (the reference slice at the operation, cut at
+//                    the contig's end - the length the BAM header gives - as FastaFileIndex::seq cuts it)
 //   6 unknown        spanning records with an I / D / N operation that also hold an operation the reference throws on ("Unknown CIGAR operation")
 // Records with more than LONG_CIGAR operations go to a wave-per-record kernel, as in the site pileup.
 #include "common.h"
@@ -48,12 +49,18 @@ __device__ __forceinline__ void indel_event(const IndelTables& w, const RecView&
 			for (int j = 0; j < avail && match; ++j) match = seq_char(r, rp + j) == (char)w.pool[q.qoff + j];
 		}
 	}
-	else if (q.kind == NGSQC_ALLELE_DEL && len == q.len)
+	else if (q.kind == NGSQC_ALLELE_DEL)
 	{
-		// "-" + reference.seq(chr, genome_pos, len): the slice holds [start, end + len) of the window, 0 behind the contig end
-		const int64_t s = q.soff + (gp - w.start[i]);
-		match = true;
-		for (int j = 0; j < len && match; ++j) match = w.pool[s + j] == w.pool[q.qoff + j];
+		// "-" + reference.seq(chr, genome_pos, len): FastaFileIndex::seq ends at the contig's end (FastaFileIndex.cpp:89-94), so a deletion running past it is
+		// compared by the bases that are left. The slice holds [start, end + q.len) of the window, 0 behind the contig end: gp <= end keeps s + q.len inside it
+		const long long left = (long long)q.ref_len - gp + 1;
+		const int have = (int)max(0ll, min((long long)len, left));
+		if (have == q.len)
+		{
+			const int64_t s = q.soff + (gp - w.start[i]);
+			match = true;
+			for (int j = 0; j < have && match; ++j) match = w.pool[s + j] == w.pool[q.qoff + j];
+		}
 	}
 	atomicAdd(&counts[8ull * i + (op == 1u ? 3 : 4)], 1u);
 	if (match) atomicAdd(&counts[8ull * i + 5], 1u);

@@ -347,7 +347,7 @@ struct IndelState
 			else { if (seen[(size_t)x.tid]) throw ArgError("windows of one reference must be contiguous"); seen[(size_t)x.tid] = 1; tf[(size_t)x.tid] = (int32_t)i; }
 			tl[(size_t)x.tid] = (int32_t)i + 1; start[(size_t)i] = x.start;
 			maxlen[(size_t)x.tid] = std::max(maxlen[(size_t)x.tid], x.end - x.start + 1);
-			IndelWin& d = win[(size_t)i]; d.end = x.end; d.kind = x.kind; d.len = x.kind == NGSQC_ALLELE_NONE ? 0 : x.len; d.pad = 0; d.qoff = (int64_t)pool.size(); d.soff = d.qoff;
+			IndelWin& d = win[(size_t)i]; d.end = x.end; d.kind = x.kind; d.len = x.kind == NGSQC_ALLELE_NONE ? 0 : x.len; d.ref_len = (int32_t)std::min<int64_t>(h->ref_lens[(size_t)x.tid], INT32_MAX); d.qoff = (int64_t)pool.size(); d.soff = d.qoff;
 			if (d.len > 0) pool.insert(pool.end(), (const uint8_t*)x.allele, (const uint8_t*)x.allele + d.len);
 			if (x.kind == NGSQC_ALLELE_DEL && d.len > 0) { d.soff = (int64_t)pool.size(); pool.insert(pool.end(), (const uint8_t*)x.ref_slice, (const uint8_t*)x.ref_slice + (x.end - x.start + d.len)); }
 		}

@@ -1132,7 +1132,8 @@ __global__ __launch_bounds__(256) void pileup_kernel(const uint8_t* __restrict__
 // the known sites inside the read - none for four reads in five. Pass 2: 64 operations per step, one per lane, coalesced; a wave prefix sum gives every operation
 // the genome / read position behind it; the sites are met in ascending order, each at the first operation that carries the genome position to or past it, exactly
 // where the sequential walk stops (BamReader.cpp:307-374): a deletion counts as deletion, a skip as nothing, anything else gives the base; a soft clip that
-// exhausts the read in front of that operation ends the walk for this and every later site (:346-353). The stream ends behind the last site of the span.
+// exhausts the read in front of that operation ends the walk for this and every later site (:346-353), and so does an operation the reference throws on (P or a
+// code above 8, :357-360: column 7 for them), whichever of the two comes first in the CIGAR. The stream ends behind the last site of the span.
 __global__ __launch_bounds__(256) void pileup_long_kernel(const uint8_t* __restrict__ infl, const int64_t* __restrict__ recoff, const int64_t* __restrict__ long_list, const unsigned long long* __restrict__ n_long_dev,
                                                           const int32_t* __restrict__ site_pos, const int32_t* __restrict__ tid_last,
                                                           const int32_t* __restrict__ bucket, const int64_t* __restrict__ tid_bucket0,
@@ -1174,7 +1175,6 @@ __global__ __launch_bounds__(256) void pileup_long_kernel(const uint8_t* __restr
 			for (uint32_t j = 0; j < 4u; ++j) if (k0 + j < r.n_cigar && ((0x18Du >> (c4[j] & 15u)) & 1u)) ref_len += c4[j] >> 4;
 		}
 		ref_len = wave_sum(ref_len);
-		const bool no_ref_ops = ref_len == 0;
 		if (ref_len == 0) ref_len = 1;   // bam_endpos
 		const int start1 = r.pos + 1, end1 = (int)(r.pos + ref_len);
 		const int last = tid_last[r.tid];
@@ -1184,10 +1184,9 @@ __global__ __launch_bounds__(256) void pileup_long_kernel(const uint8_t* __restr
 		while (cur < last && site_pos[cur] < start1) ++cur;
 		int site_end = cur; while (site_end < last && site_pos[site_end] <= end1) ++site_end;
 		if (cur >= site_end) continue;
-		if (no_ref_ops) { if (lane == 0) for (int i = cur; i < site_end; ++i) atomicAdd(&counts[8ull * i + 7], 1u); continue; }   // "Could not find position": no operation ever reaches it
 		// ---- pass 2: the operations in order ----
-		long long g_base = r.pos, rp_base = 0; bool s_seen = false;   // genome position (0-based start - 1 + consumed = 1-based position of the last consumed base) and read position behind the chunks so far
-		for (uint32_t k0 = 0; k0 < r.n_cigar && cur < site_end && !s_seen; k0 += 64u)
+		long long g_base = r.pos, rp_base = 0; bool s_seen = false, u_seen = false;   // genome position (0-based start - 1 + consumed = 1-based position of the last consumed base) and read position behind the chunks so far; the walk has ended at a soft clip / at an operation the reference throws on
+		for (uint32_t k0 = 0; k0 < r.n_cigar && cur < site_end && !s_seen && !u_seen; k0 += 64u)
 		{
 			const uint32_t k = k0 + (uint32_t)lane;
 			uint32_t op = 15u; long long len = 0;
@@ -1198,16 +1197,18 @@ __global__ __launch_bounds__(256) void pileup_long_kernel(const uint8_t* __restr
 			for (int o = 1; o < 64; o <<= 1) { const long long a = __shfl_up(g, o), b = __shfl_up(rp, o); if (lane >= o) { g += a; rp += b; } }
 			g += g_base; rp += rp_base;   // positions BEHIND this lane's operation
 			const uint64_t m_s = __builtin_amdgcn_ballot_w64(op == 4u && rp >= (long long)r.l_seq);   // soft clips that exhaust the read
+			const uint64_t m_u = __builtin_amdgcn_ballot_w64(k < r.n_cigar && (op == 6u || op > 8u));  // "Unknown CIGAR operation" (the filler lanes behind n_cigar are none)
+			const uint64_t m_end = m_s | m_u;                                                           // the walk ends at the first of these, whichever it is
 			while (cur < site_end)
 			{
 				const int pos = site_pos[cur];
 				const uint64_t m_hit = __builtin_amdgcn_ballot_w64(ref_op && g >= (long long)pos);
 				if (!m_hit) break;                                   // this site lies behind the chunk
 				const int l = __builtin_ctzll(m_hit);
-				if (m_s & ((1ull << l) - 1ull)) { s_seen = true; break; }   // the walk ended at a soft clip in front of the operation
+				if (m_end & ((1ull << l) - 1ull)) break;             // the walk ended in front of the operation
 				if (lane == l)
 				{
-					if (op == 2u) atomicAdd(&counts[8ull * cur + 5], 1u);                                            // deleted base, quality 255
+					if (op == 2u) { if (255 >= min_baseq) atomicAdd(&counts[8ull * cur + 5], 1u); }                   // deleted base, quality 255
 					else if (op != 3u)
 					{
 						const long long ap = rp - (g + 1 - pos);
@@ -1223,9 +1224,12 @@ __global__ __launch_bounds__(256) void pileup_long_kernel(const uint8_t* __restr
 				}
 				++cur;
 			}
-			if (m_s) s_seen = true;   // (a later site's operation lies behind it)
+			if (m_end) { if (m_u & (m_end & (0ull - m_end))) u_seen = true; else s_seen = true; }   // (every site left lies behind it: an unknown operation throws, a soft clip counts nothing)
 			g_base = __shfl(g, 63); rp_base = __shfl(rp, 63);
 		}
+		// the sites the walk did not decide: behind a soft clip nothing, else the reference throws ("Unknown CIGAR operation", or "Could not find position" where no
+		// operation ever reaches the site: a read without reference length)
+		if (!s_seen && lane == 0) for (int i = cur; i < site_end; ++i) atomicAdd(&counts[8ull * i + 7], 1u);
 	}
 }
 

@@ -327,7 +327,9 @@ def test_first_job_races_the_background_copy(tmp_path, monkeypatch):
     assert n_ref == 300_000
     c8, _, _, _ = job({})                                   # the default: eight walkers
     assert np.array_equal(c8, ref)
-    slow, t_open, t_h2d, _ = job({"NGSQC_H2D_PIECE_MB": "1", "NGSQC_H2D_DELAY_US": "4000", "NGSQC_H2D_THREADS": "2", "NGSQC_TILE_MEMBERS": "64"})
+    # (29 pieces, two copier threads, 50 ms per piece: the copy takes 0.7 s and open 0.03 - 0.08 s. With 4 ms per piece the copy took 0.07 s, and an open of 0.03 s
+    #  stood at 0.8 - 1.0 of the bound below: the test failed whenever the host was a little slower. An open that waited for the copy would still take as long as it)
+    slow, t_open, t_h2d, _ = job({"NGSQC_H2D_PIECE_MB": "1", "NGSQC_H2D_DELAY_US": "50000", "NGSQC_H2D_THREADS": "2", "NGSQC_TILE_MEMBERS": "64"})
     assert np.array_equal(slow, ref)
     assert t_open < 0.5 * t_h2d, (t_open, t_h2d)            # open returned long before the last piece arrived: the job ran while the copy was in flight
 
