@@ -13,7 +13,10 @@
 //              table (the literals sorted by (code length, value)), which the header pass writes to the token pool and phase 2
 //              applies. LDS per lane: a 32-byte window of the compressed input, 16 words of per-length counts / offsets, the
 //              <= 32 length symbols and <= 32 distance symbols in code order - 42 words instead of the 89 a symbol plane took,
-//              laid out element-major (word k of lane l at k*64+l: any per-lane access pattern is bank-conflict free).
+//              laid out element-major (word k of lane l at k*64+l: any per-lane access pattern is bank-conflict free). A symbol's
+//              byte says what the symbol means (extra bits and the base as a small multiplier, see len_byte / dist_byte): the
+//              trip makes length and distance from it with shifts, there is no base / extra-bits table behind it (round 11:
+//              four dependent LDS round trips per trip instead of six, 14 848 B of LDS per wave instead of 15 360).
 //            * Bit reader: a bit cursor into the input window; a trip reads the three window words under the cursor and funnels
 //              them (v_alignbit) into 64 fresh bits - no bit buffer to shift, no refill state.
 //            * Tokens leave in groups of four slots (two trips), one 16-byte store per group, into pages of a pool that the
@@ -40,8 +43,8 @@ constexpr int P1_W_RING = 0;      // compressed input window: word k of the memb
                                   // that the three words under a bit cursor are always slots s, s + 1, s + 2
 constexpr int P1_W_LINFO = 10;    // per code length l (1..15) of the literal/length code, fields on byte boundaries (the ISA reads them as sub-dword operands): literals n (bits 0..15) | first literal index << 16 | ((first non-literal index - n) & 255) << 24;
                                   // word 0: the same for the all-ones code (see LimTab); during the header passes: counts, then placement cursors
-constexpr int P1_W_NONLIT = 26;   // the symbols 256.. of the block in code order, one byte each: (symbol - 256) * 4 - LANE-major, 32 bytes per lane (round 6: the address is one v_and_or; the element-major form cost four VALU per lookup, and the decoder is what the chip's VALU issue pays for)
-constexpr int P1_W_DSYM = 34;     // the distance symbols in code order, one byte each: symbol * 4 (same layout)
+constexpr int P1_W_NONLIT = 26;   // the symbols 256.. of the block in code order, one byte each: what the symbol MEANS (len_byte below: extra bits | base, or a stop mark) - LANE-major, 32 bytes per lane (round 6: the address is one v_and_or; the element-major form cost four VALU per lookup, and the decoder is what the chip's VALU issue pays for)
+constexpr int P1_W_DSYM = 34;     // the distance symbols in code order, one byte each: dist_byte below (same layout)
 constexpr int P1_LANE_W = 42;
 constexpr int P1_RING_SLOTS = 8;
 constexpr int P1_TRIPS = 4;             // trips between two service blocks = the four words of a token group (one word per trip)
@@ -51,7 +54,6 @@ constexpr int P1_TRIPS = 4;             // trips between two service blocks = th
 constexpr int P1_WAVES_PER_SIMD = NGSQC_P1_WAVES_PER_SIMD;   // register budget of the decoder. Round 6: THREE waves per SIMD = 168 VGPRs and 8 bytes of scratch. The budget of four (128 VGPRs) is out of reach, the compiler then
                                                              // kept 193 VGPRs = TWO waves per SIMD, eight decoder waves per CU whatever the LDS allowed; with three a CU holds the ten its LDS has room for: the full-size step 444 -> 435 ms,
                                                              // K1 wall 430 -> 415 ms, although the kernel alone got slower (9.0 -> 9.6 ms per launch: the two spilled dwords), profiles/r06_schedule_probe.txt
-constexpr int P1_TAB_W = 128;     // per workgroup: base | extra bits << 16 of the symbols 256..287 (words 0..31) and the distance symbols (words 32..63); the rest is padding (an index byte of a damaged stream may point behind the tables)
 #ifndef NGSQC_P1_LINE_GROUPS
 #define NGSQC_P1_LINE_GROUPS 4
 #endif
@@ -61,10 +63,33 @@ constexpr int P1_LINE_GROUPS = NGSQC_P1_LINE_GROUPS;   // token groups a lane co
                                                        // 4 -> 441.7 ms, 446 ms: within the spread - whole lines stay (less write traffic)
 static_assert(P1_LINE_GROUPS == 2 || P1_LINE_GROUPS == 4, "line staging");
 constexpr int P1_STAGE_W = 4 * P1_LINE_GROUPS * 64;
-constexpr int P1_LDS_W = P1_LANE_W * 64 + P1_TAB_W + P1_STAGE_W;   // 15 360 B (13 312 with half lines) per one-wave workgroup
+constexpr int P1_LDS_W = P1_LANE_W * 64 + P1_STAGE_W;   // 14 848 B (12 800 with half lines) per one-wave workgroup
 
 enum { S_SYM = 0, S_NEXT = 1, S_HDR = 2, S_P1 = 3, S_P2 = 4, S_RAW = 5, S_FINISH = 6, S_DONE = 7 };   // 1..6: the slow states
-constexpr uint32_t TAB_EOB = 0x80000000u, TAB_BAD = 0x40000000u;
+
+// The symbol bytes describe themselves (round 11): RFC 1951's base tables (§3.2.5) are arithmetic, base - 3 (lengths) / base - 1 (distances) = m << extra bits
+// with a small m, so the byte holds m and the number of extra bits and the trip needs no second table behind it.
+//   length byte   : bits 0..2 extra bits eb | bits 3..6 m, SIGNED: length - 3 = ((m << eb) + extra) & 255. Symbols 257..284 have m = 0..7; symbol 285 (length 258,
+//                   no extra bits) is m = -1 (LB_258). Bit 7 = the trip stops here: LB_EOB the end of the block, LB_BAD an invalid symbol (286 / 287, or the code an
+//                   incomplete set lacks)
+//   distance byte : bits 0..3 extra bits eb | bits 4..5 m: distance - 1 = (m << eb) + extra. An invalid symbol (30 / 31, or the code an incomplete / empty set lacks) is
+//                   DB_BAD = m 3, eb 15: a distance of at least 98 305, farther back than any output of a member
+constexpr uint32_t LB_EOB = 0x80u, LB_BAD = 0xc0u, LB_258 = 0x78u, DB_BAD = 0x3fu;
+K1_DEV uint32_t len_byte(uint32_t s)    // s = symbol - 256 (0..31)
+{
+	if (s == 0) return LB_EOB;
+	if (s >= 30) return LB_BAD;
+	const uint32_t ls = s - 1;
+	if (ls < 8) return ls << 3;
+	if (ls == 28) return LB_258;
+	return ((ls - 4) >> 2) | ((4u + (ls & 3u)) << 3);
+}
+K1_DEV uint32_t dist_byte(uint32_t ds)   // ds = distance symbol (0..31)
+{
+	if (ds >= 30) return DB_BAD;
+	if (ds < 4) return ds << 4;
+	return ((ds >> 1) - 1u) | ((2u + (ds & 1u)) << 4);
+}
 
 struct P1Lds
 {
@@ -92,7 +117,7 @@ struct P1Lds
 // limit_k = 0x8000 (every code is at most k long) does not fit 15 bits: it is stored as 0x7fff, which is wrong for v = 0x7fff only - the
 // all-ones code, the last code of the longest length lmax - so the words k >= lmax describe exactly that code (LINFO word 0 / last symbol).
 // An incomplete code (zlib accepts a single code of length 1, and an empty distance code): the words k >= lmax decode - as a code of length 1 - to entries 30 / 31
-// of the symbol bytes, which the header pass points at invalid entries of the base / extra-bits table.
+// of the symbol bytes, where the header pass writes the bytes of an invalid symbol (LB_BAD / DB_BAD).
 constexpr uint32_t W0_L = (1u << 12) | (1u << 8) | 31u, W0_D = (1u << 12) | 31u;   // W_0: limit 0, length 1, first symbol 0
 struct LimTab
 {
@@ -123,7 +148,7 @@ struct LimTab
 		if ((uint32_t)k < lmax) return (lim << 17) | ((uint32_t)(k + 1) << 12) | (dist ? off << 6 : (uint32_t)(k + 1) << 8) | (uint32_t)(32 - (k + 1));
 		if (!incomplete) return (0x7fffu << 17) | (lmax << 12) | (dist ? (total - 1) << 6 : 0u) | (32u - lmax);
 		// an incomplete code (one code of length 1, or no code): what lies behind it decodes - as a code of length 1, index 0 or 1 - to entries 30 / 31 of the symbol
-		// bytes, which the header pass points at the invalid entries of the base / extra-bits table (the symbol loop has no test of its own for this)
+		// bytes, where the header pass writes LB_BAD / DB_BAD (the symbol loop has no test of its own for this)
 		return (lim << 17) | (1u << 12) | (dist ? 30u << 6 : 0u) | 31u;
 	}
 };
@@ -146,38 +171,7 @@ K1_KERNEL_OCC(64, P1_WAVES_PER_SIMD) void huff_tokens_kernel(const uint8_t* __re
 	P1Lds L{lds, lane};
 	wv::set_priority(park_hi >> 8); park_hi &= 255;   // (upper bits: wave priority of the decoder waves - always 0 since the launcher's priority probe is finished)
 	const wv::u32x4* const comp_q = (const wv::u32x4*)comp;
-	uint32_t* const tab = lds + P1_LANE_W * 64;
-	uint32_t* const stage = lds + P1_LANE_W * 64 + P1_TAB_W + lane * (4 * P1_LINE_GROUPS);   // lane-major; a lane's four groups rotated by lane / 4, so that sixteen lanes' 16-byte accesses meet sixteen different bank quads
-	{
-		// RFC 1951 §3.2.5: symbol 256 ends the block, 257..285 are the 29 length symbols, 286/287 (only in the fixed code) are invalid; 30 distance symbols
-		const uint32_t i = (uint32_t)lane;
-		if (i < 32)
-		{
-			uint32_t v = TAB_BAD | TAB_EOB;   // (286 / 287 and the entries an incomplete code decodes to: they leave the symbol loop the way the end of a block does)
-			if (i == 0) v = TAB_EOB;
-			else if (i < 30)
-			{
-				const uint32_t ls = i - 1;
-				const uint32_t eb = ls < 8 ? 0u : (ls == 28 ? 0u : (ls - 4) >> 2);
-				const uint32_t bs = ls < 8 ? ls + 3 : (ls == 28 ? 258u : ((4u + ((ls - 4) & 3u)) << eb) + 3u);
-				v = bs | (eb << 16);
-			}
-			tab[i] = v;
-		}
-		else
-		{
-			const uint32_t ds = i - 32;
-			uint32_t v = TAB_BAD;
-			if (ds < 30)
-			{
-				const uint32_t eb = ds < 4 ? 0u : (ds >> 1) - 1u;
-				const uint32_t bs = ds < 4 ? ds + 1 : ((2u + (ds & 1u)) << eb) + 1u;
-				v = bs | (eb << 16);
-			}
-			tab[i] = v;
-		}
-	}
-	wv::barrier();
+	uint32_t* const stage = lds + P1_LANE_W * 64 + lane * (4 * P1_LINE_GROUPS);   // lane-major; a lane's four groups rotated by lane / 4, so that sixteen lanes' 16-byte accesses meet sixteen different bank quads
 
 	// ---- per-lane decoder state (what lives across the symbol loop) ----
 	uint32_t state = S_NEXT;
@@ -247,7 +241,7 @@ K1_KERNEL_OCC(64, P1_WAVES_PER_SIMD) void huff_tokens_kernel(const uint8_t* __re
 	// One trip of the symbol loop: up to two literal/length symbols and one distance. At most 15 + (15 + 5) + (15 + 13) = 63 bits.
 	// alim: the lane decodes while its cursor is in front of this bit (set by the service block: the window words in front of it are staged, or the member has no
 	// more input; 0: the lane does not decode). Round 6, an instruction diet (the decoder's VALU count is what the pipelined K1 pays for): no test for invalid codes
-	// (an incomplete code decodes to table entries that end the loop / fail the distance check), LINFO fields and symbol bytes on byte boundaries.
+	// (an incomplete code decodes to symbol bytes that end the loop / fail the distance check), LINFO fields and symbol bytes on byte boundaries.
 	auto trip = [&](uint32_t& slot, uint32_t& alim) {
 		const bool act = abit < alim;
 		const uint32_t* p = L.ring(abit);
@@ -266,25 +260,26 @@ K1_KERNEL_OCC(64, P1_WAVES_PER_SIMD) void huff_tokens_kernel(const uint8_t* __re
 		const uint32_t e = lit1 ? tb + (li2 >> 24) : ta + (li1 >> 24);   // index in code order (mod 32: sym_byte masks it)
 		const uint32_t ub = lit1 ? len1 + len2 : len1;                   // bits up to and including its code (<= 30); both literals: the bits of the trip
 		const bool nonlit = !(lit1 && lit2);
-		const uint32_t lt = *(const uint32_t*)((const uint8_t*)tab + L.sym_byte(P1_W_NONLIT, e));
-		const uint32_t eb = wv::bfe(lt, 16, 3);
-		const uint32_t mlen = (lt & 0x1ffu) + wv::bfe(wv::alignbit(w1, w0, ub), 0, eb);
+		const uint32_t lb = L.sym_byte(P1_W_NONLIT, e);                 // the length byte (see len_byte)
+		const uint32_t eb = lb & 7u;
+		const uint32_t mm = (((uint32_t)((int32_t)(lb << 25) >> 28) << eb) + wv::bfe(wv::alignbit(w1, w0, ub), 0, eb)) & 255u;   // length - 3 (m = the signed field at bits 3..6: one v_bfe_i32)
 		const uint32_t u2 = ub + eb;                                     // <= 35
 		const uint32_t wd = (uint32_t)((((uint64_t)w1 << 32) | w0) >> u2);   // >= 29 valid bits: a distance takes at most 28
 		uint32_t sd, td;
 		limD.decode(W0_D, wd, sd, td);
 		const uint32_t dl = wv::bfe(sd, 12, 4);
-		const uint32_t dt = *(const uint32_t*)((const uint8_t*)tab + 128 + L.sym_byte(P1_W_DSYM, td + wv::bfe(sd, 6, 5)));
-		const uint32_t deb = wv::bfe(dt, 16, 4);
-		const uint32_t mdist = (dt & (TAB_BAD | 0x7fffu)) + wv::bfe(wd, dl, deb);   // (an invalid distance symbol: farther back than any output)
-		const bool stop = nonlit && (int32_t)lt < 0, match = nonlit && (int32_t)lt >= 0;   // stop: the end of the block, or an invalid length symbol
+		const uint32_t db = L.sym_byte(P1_W_DSYM, td + wv::bfe(sd, 6, 5));   // the distance byte (see dist_byte)
+		const uint32_t deb = db & 15u;
+		const uint32_t md = (wv::bfe(db, 4, 2) << deb) + wv::bfe(wd, dl, deb);   // distance - 1 (an invalid distance symbol: farther back than any output)
+		const bool is_len = lb < LB_EOB;
+		const bool stop = nonlit && !is_len, match = nonlit && is_len;   // stop: the end of the block, or an invalid length symbol (one compare, its inverse in the scalar unit)
 		const uint32_t used = match ? u2 + dl + deb : ub;
-		const uint32_t tokm = (mlen << 15) + mdist - ((3u << 15) + 1u);                 // = (mlen - 3) << 15 | (mdist - 1)
+		const uint32_t tokm = (mm << 15) + md;                                         // = (length - 3) << 15 | (distance - 1)
 		// the output position behind the trip's literals, then behind its match (a lane that does not decode adds nothing). A trip that turns out bad
 		// still writes its word and moves the cursors: the member ends with an error and phase 2 never looks at its tokens
 		const uint32_t o1 = out_n + ((act && lit1) ? 1u : 0u) + ((act && lit1 && lit2) ? 1u : 0u);
-		const uint32_t o2 = o1 + ((act && match) ? mlen : 0u);
-		const bool bad = (match && mdist > o1) || o2 > usize;
+		const uint32_t o2 = (act && match) ? o1 + mm + 3u : o1;   // (one v_add3 and a select)
+		const bool bad = (match && md >= o1) || o2 > usize;
 		if ((alim != 0) & !act) K1_STAT(3);
 		// the trip's word: two literals | a literal, then a match | a literal (in front of the end of the block) | a match | nothing
 		const uint32_t w_lit = lit2 ? (K1_TOK_LIT2 | tok1 | (tok2 << 8)) : (match ? (K1_TOK_LITMATCH | (tok1 << 23) | tokm) : tok1);
@@ -295,8 +290,8 @@ K1_KERNEL_OCC(64, P1_WAVES_PER_SIMD) void huff_tokens_kernel(const uint8_t* __re
 		if (act && (bad || stop))
 		{
 			alim = 0;
-			if (bad) { err = !match ? 3u : (dt & TAB_BAD) ? 12u : mdist > o1 ? 13u : 3u; state = S_FINISH; }
-			else if (lt & TAB_BAD) { err = 10u; state = S_FINISH; }   // 286 / 287, or a code that does not exist in an incomplete set
+			if (bad) { err = !match ? 3u : db == DB_BAD ? 12u : md >= o1 ? 13u : 3u; state = S_FINISH; }
+			else if (lb != LB_EOB) { err = 10u; state = S_FINISH; }   // 286 / 287, or a code that does not exist in an incomplete set
 			else state = bfinal ? (uint32_t)S_FINISH : (uint32_t)S_HDR;
 		}
 	};
@@ -472,8 +467,8 @@ K1_KERNEL_OCC(64, P1_WAVES_PER_SIMD) void huff_tokens_kernel(const uint8_t* __re
 								{
 									const uint32_t i = h_i + k; uint32_t li = L.linfo(val);
 									if (i < 256u) { ((uint8_t*)pool)[(uint64_t)cur_tab * 4u + (li & 511u)] = (uint8_t)i; li += 1u; }
-									else if (i < h_nlit) { L.sym_byte(P1_W_NONLIT, (li >> 9) & 511u) = (uint8_t)((i - 256u) * 4u); li += 1u << 9; }
-									else { L.sym_byte(P1_W_DSYM, li >> 18) = (uint8_t)((i - h_nlit) * 4u); li += 1u << 18; }
+									else if (i < h_nlit) { L.sym_byte(P1_W_NONLIT, (li >> 9) & 511u) = (uint8_t)len_byte(i - 256u); li += 1u << 9; }
+									else { L.sym_byte(P1_W_DSYM, li >> 18) = (uint8_t)dist_byte(i - h_nlit); li += 1u << 18; }
 									L.linfo(val) = li;
 								}
 							}
@@ -526,9 +521,9 @@ K1_KERNEL_OCC(64, P1_WAVES_PER_SIMD) void huff_tokens_kernel(const uint8_t* __re
 									}
 									L.linfo(0) = last_non ? (((pb - 1u) & 255u) << 24) : (1u | (((pa - 1u) & 255u) << 16));   // the all-ones code: the last symbol of the longest length
 									// an incomplete set (the check above let it pass: a single code of length 1 / no distance code): the decode words of the bits behind its codes
-									// lead to entries 30 and 31 of the symbol bytes (free: at most one symbol is in use) - the invalid entries of the base / extra-bits tables
-									if (leftL > 0) { L.linfo(0) = 30u << 24; L.sym_byte(P1_W_NONLIT, 30u) = 30u * 4u; L.sym_byte(P1_W_NONLIT, 31u) = 31u * 4u; }
-									if (leftD > 0) { L.sym_byte(P1_W_DSYM, 30u) = 30u * 4u; L.sym_byte(P1_W_DSYM, 31u) = 31u * 4u; }
+									// lead to entries 30 and 31 of the symbol bytes (free: at most one symbol is in use), which get the bytes of an invalid symbol
+									if (leftL > 0) { L.linfo(0) = 30u << 24; L.sym_byte(P1_W_NONLIT, 30u) = (uint8_t)LB_BAD; L.sym_byte(P1_W_NONLIT, 31u) = (uint8_t)LB_BAD; }
+									if (leftD > 0) { L.sym_byte(P1_W_DSYM, 30u) = (uint8_t)DB_BAD; L.sym_byte(P1_W_DSYM, 31u) = (uint8_t)DB_BAD; }
 									state = S_SYM;
 								}
 							}
