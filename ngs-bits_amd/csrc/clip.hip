@@ -63,7 +63,7 @@ __global__ __launch_bounds__(256) void clip_keys_kernel(const uint8_t* __restric
 				RecView r = load_rec(infl, recoff[i]); rec_apply_cg(r);
 				src[e] = (uint64_t)(uintptr_t)(infl + recoff[i]);
 				const bool j = joins(r);
-				key[e] = j ? name_hash(r.core + 32, r.l_name ? (int)r.l_name - 1 : 0) & mask : KEY_NONE;
+				key[e] = j ? rec_name_hash(r) & mask : KEY_NONE;
 				info[e] = INFO_PASS | ((uint32_t)(ord_base + i) & INFO_ORD);
 				jn[i] = j ? 1 : 0;
 				bases = r.l_seq; pass = j ? 0 : 1;

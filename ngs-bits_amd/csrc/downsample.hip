@@ -167,7 +167,7 @@ __global__ __launch_bounds__(256) void ds_keys_kernel(const uint8_t* __restrict_
 		if (r.flag & 0x900) { key[e] = KEY_NONE; info[e] = 0; se[i] = 0; continue; }
 		info[e] = out_size(r) | 0x80000000u;
 		se[i] = (r.flag & 1) ? 0 : 1;
-		key[e] = (r.flag & 1) ? name_hash(r.core + 32, r.l_name ? (int)r.l_name - 1 : 0) & mask : KEY_NONE;
+		key[e] = (r.flag & 1) ? rec_name_hash(r) & mask : KEY_NONE;
 	}
 }
 
@@ -191,7 +191,7 @@ __global__ __launch_bounds__(256) void ds_sizes_kernel(const int64_t* __restrict
 		if (se[i]) { atomicAdd(&counts[C_SE], 1ull); if (kept) { atomicAdd(&counts[C_SE_PASS], 1ull); v = info[H + i] & 0x7fffffffu; } }
 		else if (kept) { atomicAdd(&counts[C_PE_PASS], 1ull); v = (uint64_t)(info[close_of[i] >> 1] & 0x7fffffffu) + (info[H + i] & 0x7fffffffu); }
 		sz[i] = v;
-		if (nsz) { const uint32_t ln = ((const uint8_t*)(uintptr_t)src[H + i])[12]; nsz[i] = kept ? 4ull + (ln ? ln - 1 : 0) : 0; }
+		if (nsz) nsz[i] = kept ? 4ull + (uint64_t)rec_name_len((const uint8_t*)(uintptr_t)src[H + i]) : 0;
 	}
 }
 

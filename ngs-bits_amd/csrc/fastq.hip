@@ -12,6 +12,7 @@
 //   4. format: an exclusive scan over the entry sizes per stream, then a wave per entry writing it at its offset - whole dwords inside, bytes at the ragged
 //      ends - into that stream's window (an entry that straddles two windows is written in two launches). Whole pieces go through the encoder at the level.
 #include "join.h"
+#include "tofastq_visit.h"
 #include <rocprim/device/device_merge.hpp>
 #include <rocprim/device/device_reduce.hpp>
 
@@ -21,53 +22,7 @@ namespace {
 struct FqParams { int32_t remove_dup, fix, extend, paired; int32_t reg_tid, reg_start, reg_end; uint64_t mask; };
 
 enum { C_UNPAIRED, C_SINGLE, C_DUP, C_FIXED, N_FQ_COUNTS };
-constexpr uint32_t INFO_KEPT = 0x80000000u, INFO_THROWS = 0x40000000u, INFO_SIZE = 0x3fffffffu;
-
-__constant__ char c_nt16[16] = {'=', 'A', 'C', 'M', 'G', 'R', 'S', 'V', 'T', 'W', 'Y', 'H', 'K', 'D', 'B', 'N'};
-__constant__ char c_comp16[16] = {'N', 'T', 'G', 'N', 'C', 'N', 'N', 'N', 'A', 'N', 'N', 'N', 'N', 'N', 'N', 'N'};   // (only ACGTN have a complement: the rest throws)
-
-__device__ __forceinline__ int base_code(const uint8_t* seq, int j) { return (seq[j >> 1] >> ((~j & 1) << 2)) & 15; }
-__device__ __forceinline__ bool has_complement(int c) { return c == 1 || c == 2 || c == 4 || c == 8 || c == 15; }
-
-// bam_endpos of htslib (the effective CIGAR; an unmapped record or an empty span counts one base)
-__device__ int64_t rec_endpos(RecView r)
-{
-	rec_apply_cg(r);
-	int64_t rlen = 0;
-	if (!(r.flag & 4))
-		for (uint32_t i = 0; i < r.n_cigar; ++i) { const uint32_t c = ld32(r.cigar + 4ull * i), op = c & 15u; if (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) rlen += c >> 4; }
-	return (int64_t)r.pos + (rlen ? rlen : 1);
-}
-
-// the bytes of an entry: "@name\n" BASES "\n+\n" QUALS "\n"; qcut: the quality bytes gzputs writes (up to the first NUL)
-struct FqEntry { const uint8_t* name; const uint8_t* seq; const uint8_t* qual; int nl, lseq, L, qcut; bool rev; };
-__device__ __forceinline__ FqEntry fq_entry(const uint8_t* rec, uint32_t size, int extend)
-{
-	const RecView r = load_rec(rec, 0);
-	FqEntry e;
-	e.nl = r.l_name ? (int)r.l_name - 1 : 0; e.name = r.core + 32; e.lseq = r.l_seq; e.L = max(r.l_seq, extend);
-	e.seq = r.cigar + 4ull * r.n_cigar_raw; e.qual = rec_qual(r); e.rev = (r.flag & 0x10) != 0;
-	e.qcut = (int)size - (e.nl + e.L + 6);
-	return e;
-}
-__device__ __forceinline__ uint8_t fq_byte(const FqEntry& e, int k)
-{
-	if (k == 0) return '@';
-	k -= 1; if (k < e.nl) return e.name[k];
-	k -= e.nl; if (k == 0) return '\n';
-	k -= 1;
-	if (k < e.L)
-	{
-		if (k >= e.lseq) return 'N';
-		return e.rev ? (uint8_t)c_comp16[base_code(e.seq, e.lseq - 1 - k)] : (uint8_t)c_nt16[base_code(e.seq, k)];
-	}
-	k -= e.L;
-	if (k == 0 || k == 2) return '\n';
-	if (k == 1) return '+';
-	k -= 3;
-	if (k < e.qcut) return k >= e.lseq ? (uint8_t)'#' : (uint8_t)(e.qual[e.rev ? e.lseq - 1 - k : k] + 33);
-	return '\n';
-}
+// (the region rule, the entry's info word, fq_entry / fq_byte and a lane's share of an entry: tofastq_visit.h)
 
 // entries: [0, H) held, [H, H + n) the tile's records. key: KEY_NONE here (set by fq_join_keys_kernel); info = entry size | kept | throws.
 // fkey: (name hash << 1 | read 1) of a candidate, KEY_NONE for a record that steps 1-2 skip; cand: the record reaches the -fix / mate-cache steps
@@ -84,29 +39,22 @@ __global__ __launch_bounds__(256) void fq_keys_kernel(const uint8_t* __restrict_
 		const uint8_t* q = infl + recoff[i];
 		const RecView r = load_rec(infl, recoff[i]);
 		src[e] = (uint64_t)(uintptr_t)q; key[e] = KEY_NONE; info[e] = 0; fkey[i] = KEY_NONE; fidx[i] = (uint32_t)i; cand[i] = 0;
-		if (p.reg_tid >= 0 && !(r.tid == p.reg_tid && r.pos < p.reg_end && rec_endpos(r) > (int64_t)p.reg_start - 1)) continue;
+		if (p.reg_tid >= 0 && !fq_in_region(r, p.reg_tid, p.reg_start, p.reg_end)) continue;
 		if (r.flag & 0x900) continue;
 		if (p.remove_dup && (r.flag & 0x400)) { atomicAdd(&counts[C_DUP], 1ull); continue; }
-		// the entry: header, bases (extended), "+", qualities up to the first NUL of the oriented, extended line
-		const int nl = r.l_name ? (int)r.l_name - 1 : 0, L = max(r.l_seq, p.extend);
-		const uint8_t* qu = rec_qual(r); const uint8_t* sq = r.cigar + 4ull * r.n_cigar_raw;
-		const bool rev = (r.flag & 0x10) != 0;
-		int qcut = L;
-		if (!rev) { for (int j = 0; j < r.l_seq; ++j) if (qu[j] == 223) { qcut = j; break; } }
-		else { for (int j = r.l_seq - 1; j >= 0; --j) if (qu[j] == 223) { qcut = r.l_seq - 1 - j; break; } }
-		bool throws = false;
-		if (rev) for (int j = 0; j < r.l_seq && !throws; ++j) throws = !has_complement(base_code(sq, j));
-		info[e] = (uint32_t)(nl + L + qcut + 6) | INFO_KEPT | (throws ? INFO_THROWS : 0u);
-		fkey[i] = (name_hash(r.core + 32, nl) & p.mask) << 1 | ((r.flag & 0x40) ? 1u : 0u);
+		int nl;
+		const uint64_t hash = name_hash_z(r.core + 32, r.l_name, nl);
+		info[e] = fq_entry_info(r, p.extend, nl);
+		fkey[i] = (hash & p.mask) << 1 | ((r.flag & 0x40) ? 1u : 0u);
 		cand[i] = 1;
 	}
 }
 
-// -fix: the persistent set (keys sorted, values = arena offsets of [l_name][name bytes])
+// -fix: the persistent set (keys sorted, values = arena offsets of [name length][name bytes]; the name as join_visit.h's name_len gives it, at most 255 bytes)
 __device__ __forceinline__ bool arena_same_name(const uint8_t* a, const uint8_t* rec)
 {
 	const uint32_t la = a[0];
-	if (la != rec[12]) return false;
+	if (la != (uint32_t)rec_name_len(rec)) return false;
 	for (uint32_t i = 0; i < la; ++i) if (a[1 + i] != rec[36 + i]) return false;
 	return true;
 }
@@ -133,7 +81,7 @@ __global__ __launch_bounds__(256) void fq_fix_kernel(const uint64_t* __restrict_
 			for (int64_t m = lo; m < S && set_k[m] == k && !seen; ++m) seen = arena_same_name(arena + set_v[m], a);
 			for (int64_t r = j; r < q && !seen; ++r) seen = wn[r] && same_name((const uint8_t*)(uintptr_t)src[H + is[r]], a);
 			if (seen) { wn[q] = 0; cand[is[q]] = 0; atomicAdd(&counts[C_FIXED], 1ull); }
-			else wn[q] = 1ull << 40 | (1ull + a[12]);
+			else wn[q] = 1ull << 40 | (1ull + (uint64_t)rec_name_len(a));
 		}
 	}
 }
@@ -148,7 +96,7 @@ __global__ __launch_bounds__(256) void fq_fix_store_kernel(const uint64_t* __res
 		if (!wn[q]) continue;
 		const uint64_t slot = wo[q] >> 40, off = arena_used + (wo[q] & ((1ull << 40) - 1));
 		const uint8_t* a = (const uint8_t*)(uintptr_t)src[H + is[q]];
-		const uint32_t la = a[12];
+		const uint32_t la = (uint32_t)rec_name_len(a);
 		arena[off] = (uint8_t)la;
 		for (uint32_t i = 0; i < la; ++i) arena[off + 1 + i] = a[36 + i];
 		wk[slot] = ks[q]; wv[slot] = off;
@@ -222,23 +170,9 @@ __global__ __launch_bounds__(256) void fq_format_kernel(const uint64_t* __restri
 		const int64_t size = (int64_t)sz[i];
 		if (!size) continue;
 		const int64_t pos = (int64_t)off[i] - ws;
-		const int64_t a = max(pos, w.lo), b = min(pos + size, w.hi);
-		if (a >= b) continue;
-		const FqEntry e = fq_entry((const uint8_t*)(uintptr_t)rp[i], (uint32_t)size, extend);
-		const int64_t d0 = (a + 3) & ~3ll, d1 = b & ~3ll;
-		if (d0 >= d1)
-		{
-			for (int64_t x = a + lane; x < b; x += 64) w.base[x] = fq_byte(e, (int)(x - pos));
-			continue;
-		}
-		if (lane < d0 - a) w.base[a + lane] = fq_byte(e, (int)(a + lane - pos));
-		if (lane >= 8 && lane - 8 < b - d1) w.base[d1 + lane - 8] = fq_byte(e, (int)(d1 + lane - 8 - pos));
-		uint32_t* dw = reinterpret_cast<uint32_t*>(w.base);
-		for (int64_t x = d0 + 4 * lane; x < d1; x += 256)
-		{
-			const int k = (int)(x - pos);
-			dw[x >> 2] = (uint32_t)fq_byte(e, k) | (uint32_t)fq_byte(e, k + 1) << 8 | (uint32_t)fq_byte(e, k + 2) << 16 | (uint32_t)fq_byte(e, k + 3) << 24;
-		}
+		const FqSplit sp = fq_split(pos, size, w.lo, w.hi);
+		if (sp.a >= sp.b) continue;
+		fq_format_lane(fq_entry((const uint8_t*)(uintptr_t)rp[i], (uint32_t)size, extend), pos, sp, lane, w.base);
 	}
 }
 

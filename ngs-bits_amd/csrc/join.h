@@ -1,8 +1,8 @@
 // The mate join by read name and the windowed BGZF writer, shared by the tools that pair records and / or write compressed output (NameJoin: BamFilter pairs.hip,
 // BamToFastq fastq.hip, BamDownsample downsample.hip, BamRemoveVariants rmvar.hip, BamClipOverlap clip.hip; BgzfStream: those and BamExtract extract.hip,
 // BamCleanHaloplex haloplex.hip). One pass over the tiles; per tile (NameJoin):
-//   1. the tool's keys kernel gives every tile record a 64-bit name hash (KEY_NONE: the record takes no part), its source pointer and a 32-bit info word whose
-//      bit 31 says the record is kept ("passes"); val[e] = e for every entry.
+//   1. the tool's keys kernel gives every tile record a 64-bit hash of its name (join_visit.h: the bytes in front of the first NUL; KEY_NONE: the record takes
+//      no part), its source pointer and a 32-bit info word whose bit 31 says the record is kept ("passes"); val[e] = e for every entry.
 //   2. sort: the open entries carried over from earlier tiles ("held", in (hash, ordinal) order) followed by the tile's records, radix-sorted by hash (rocPRIM,
 //      stable: within a hash the order stays the file order).
 //   3. resolve: one thread per run of equal hashes. When every name of the run is the same, the run pairs (0,1), (2,3), ... and an odd last entry stays open;
@@ -16,42 +16,12 @@
 // scan_u64 / scan_tmp_bytes: the one checked rocPRIM exclusive sum of the join, of place and of the tools' own scans.
 #pragma once
 #include "handle.h"
-#include "rec.h"
+#include "join_visit.h"
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 
 namespace ngsqc {
 namespace {
-constexpr uint64_t KEY_NONE = ~0ull;
-
-__device__ __forceinline__ uint64_t name_hash(const uint8_t* p, int n)   // FNV-1a, then a 64-bit finaliser (splitmix64)
-{
-	uint64_t h = 0xcbf29ce484222325ull;
-	for (int i = 0; i < n; ++i) h = (h ^ p[i]) * 0x100000001b3ull;
-	h ^= h >> 30; h *= 0xbf58476d1ce4e5b9ull; h ^= h >> 27; h *= 0x94d049bb133111ebull; h ^= h >> 31;
-	return h;
-}
-
-// test hook NGSQC_NAME_HASH_BITS (CallSwitches::name_hash_bits, 1 .. 63): fewer hash bits, collisions everywhere
-inline uint64_t name_hash_mask(int bits) { return bits >= 63 ? (~0ull >> 1) : ((1ull << bits) - 1); }
-
-__device__ __forceinline__ bool same_name(const uint8_t* a, const uint8_t* b)
-{
-	const uint32_t la = a[12], lb = b[12];
-	if (la != lb) return false;
-	for (uint32_t i = 0; i < la; ++i) if (a[36 + i] != b[36 + i]) return false;
-	return true;
-}
-
-struct ResolveOut { int64_t* close_of; uint8_t* held; uint8_t* st; unsigned long long* counts; };   // close_of[tile record] = opener entry << 1 | kept; held / st: per sorted position
-
-__device__ __forceinline__ void close_pair(const ResolveOut& o, const uint32_t* info, int64_t H, uint32_t oe, uint32_t ce)
-{
-	const bool kept = (info[oe] >> 31) && (info[ce] >> 31);
-	o.close_of[ce - H] = (int64_t)oe << 1 | (kept ? 1 : 0);   // (a closer is always a tile record: every held entry lies before the tile)
-	atomicAdd(&o.counts[kept ? 0 : 1], 1ull);
-}
-
 __global__ __launch_bounds__(256) void join_resolve_kernel(const uint64_t* __restrict__ ks, const uint32_t* __restrict__ vs, int64_t N, int64_t H, const uint64_t* __restrict__ src,
                                                            const uint32_t* __restrict__ info, ResolveOut o)
 {
@@ -60,33 +30,11 @@ __global__ __launch_bounds__(256) void join_resolve_kernel(const uint64_t* __res
 	{
 		const uint64_t k = ks[j];
 		if (k == KEY_NONE || (j > 0 && ks[j - 1] == k)) continue;
-		int64_t e = j + 1;
-		while (e < N && ks[e] == k) ++e;
-		const uint8_t* first = (const uint8_t*)(uintptr_t)src[vs[j]];
-		bool same = true;
-		for (int64_t q = j + 1; q < e && same; ++q) same = same_name(first, (const uint8_t*)(uintptr_t)src[vs[q]]);
-		if (same)
-		{
-			int64_t q = j;
-			for (; q + 1 < e; q += 2) close_pair(o, info, H, vs[q], vs[q + 1]);
-			if (q < e) o.held[q] = 1;
-		}
-		else   // a hash collision: pair name by name, in file order
-		{
-			for (int64_t q = j; q < e; ++q)
-			{
-				const uint8_t* a = (const uint8_t*)(uintptr_t)src[vs[q]];
-				int64_t f = -1;
-				for (int64_t r = j; r < q && f < 0; ++r) if (o.st[r] == 1 && same_name((const uint8_t*)(uintptr_t)src[vs[r]], a)) f = r;
-				if (f >= 0) { o.st[f] = 2; o.st[q] = 2; close_pair(o, info, H, vs[f], vs[q]); }
-				else o.st[q] = 1;
-			}
-			for (int64_t q = j; q < e; ++q) o.held[q] = o.st[q] == 1 ? 1 : 0;
-		}
+		join_resolve_run(ks, vs, N, H, src, info, o, j);   // (join_visit.h)
 	}
 }
 
-// the bytes a held entry keeps: the whole record when it passes, else the fixed part and the name (all a later name comparison reads)
+// the bytes a held entry keeps (join_visit.h held_entry_bytes)
 __global__ __launch_bounds__(256) void held_bytes_kernel(const uint8_t* __restrict__ held, const uint32_t* __restrict__ vs, int64_t N, const uint64_t* __restrict__ src, const uint32_t* __restrict__ info, uint64_t* __restrict__ nb)
 {
 	const int64_t stride = (int64_t)gridDim.x * blockDim.x;
@@ -94,7 +42,7 @@ __global__ __launch_bounds__(256) void held_bytes_kernel(const uint8_t* __restri
 	{
 		if (!held[j]) { nb[j] = 0; continue; }
 		const uint8_t* s = (const uint8_t*)(uintptr_t)src[vs[j]];
-		nb[j] = (info[vs[j]] >> 31) ? (uint64_t)ld32(s) + 4 : 36ull + s[12];
+		nb[j] = held_entry_bytes(s, (info[vs[j]] >> 31) != 0);
 	}
 }
 

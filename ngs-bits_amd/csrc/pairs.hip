@@ -48,7 +48,7 @@ __global__ __launch_bounds__(256) void pair_keys_kernel(const uint8_t* __restric
 		const RecView r = load_rec(infl, recoff[i]);
 		src[e] = (uint64_t)(uintptr_t)q;
 		if (r.flag & 0x900) { key[e] = KEY_NONE; info[e] = 0; continue; }
-		key[e] = name_hash(r.core + 32, r.l_name ? (int)r.l_name - 1 : 0) & p.mask;
+		key[e] = rec_name_hash(r) & p.mask;
 		info[e] = out_size(r) | (alignment_pass(r, p) ? 0x80000000u : 0u);
 	}
 }

@@ -96,7 +96,7 @@ __global__ __launch_bounds__(256) void rm_verdict_kernel(const uint8_t* __restri
 			if (o.key) { o.info[e] = 0; atomicAdd(&o.counts[C_SKIPPED], 1ull); }
 			continue;
 		}
-		if (o.key && !m.single_end) o.key[e] = name_hash(r.core + 32, r.l_name ? (int)r.l_name - 1 : 0) & hash_mask;
+		if (o.key && !m.single_end) o.key[e] = rec_name_hash(r) & hash_mask;
 		const RecView raw = r;
 		rec_apply_cg(r);
 		if (r.n_cigar > (uint32_t)LONG_CIGAR) { long_list[atomicAdd(long_count, 1ull)] = i; continue; }   // wave-per-record path (rm_long_kernel)

@@ -31,7 +31,8 @@ class Rec:
         self.b = b
         (self.bs, self.tid, self.pos, self.l_name, self.mapq, self.bin, self.n_cigar, self.flag, self.l_seq, self.mtid, self.mpos,
          self.isize) = struct.unpack_from("<IiiBBHHHiiii", b, 0)
-        self.name = b[36:36 + self.l_name - 1] if self.l_name else b""
+        # BamAlignment::name() (src/cppNGS/BamReader.h:69-72): bam_get_qname read as a C string - the bytes of the name field in front of its first NUL
+        self.name = b[36:36 + self.l_name].split(b"\0", 1)[0]
         self.cig_off = 36 + self.l_name
         self.cigar = list(struct.unpack_from(f"<{self.n_cigar}I", b, self.cig_off))
         self.seq_off = self.cig_off + 4 * self.n_cigar
