@@ -593,25 +593,29 @@ constexpr int P2_HIST = 16;                    // output bytes in front of the b
 constexpr int P2_IMAX = 192;                   // items per batch: a batch is cut so that its items fill whole steps of 64 (round 6: 129 -> 109 steps per member of the bench data)
 constexpr int P2_NW = P2_BMAX / 32 + 1;        // words of the item-start bit mask (one lane each in the count scan)
 constexpr int P2_LONG = P2_IMAX / 2;           // matches of more than 16 bytes in a batch (each has at least two items)
-constexpr int P2_TRASH = P2_BMAX + 15;         // a staging byte nobody reads: where the stores of lanes without a literal go (no branch around a store)
 static_assert(P2_BMAX >= 4 * 259 && P2_BMAX < 2048 && P2_BMAX % 8 == 0 && P2_NW <= 64 && P2_HIST % 4 == 0 && P2_IMAX >= 4 * 17 && P2_IMAX % 64 == 0, "phase-2 batch geometry");
 // item word: first byte (batch-relative) | (length - 1) << 11 | (distance - 1) << 15; a raw run: bit 31 | payload offset << 15. An item of a distance-1 match
 // (a run of one byte: the usual self-overlapping match of BAM data) carries bit 30 and the distance to the byte IN FRONT OF THE MATCH instead: every item of
 // the run repeats that byte, none of them waits for its predecessor
 struct P2Lds
 {
-	uint32_t it[P2_IMAX + 8];                              // (the last word: where the item words of lanes without an item go)
+	uint32_t it[P2_IMAX + 8];                              // (the eight words behind P2_IMAX are unused since round 12; they stay because dropping them moves every array behind them: a layout of its own to measure)
 	uint32_t ib[2 * 64];                                   // per 32 output bytes: {bit mask of the first bytes of NEAR items, near items that start in front of them}
-	uint32_t lg[2 * P2_LONG + 8];                            // the batch's matches of more than 16 bytes: {first byte | length << 11 | index of the first item << 20, key}; then (pass A / B) the near items
+	uint32_t lg[2 * P2_LONG + 8];                            // (+ 8: unused since round 12, as above) the batch's matches of more than 16 bytes: {first byte | length << 11 | index of the first item << 20, key}; then (pass A / B) the near items
 	alignas(16) uint8_t val[P2_HIST + P2_BMAX + 16];       // [history | the batch's bytes | slack]
 	alignas(4) uint8_t lit[256];                           // the literal table of the current DEFLATE block
 };
 
 // Round 6: the kernel's instruction count, not its memory traffic, is what the pipelined K1 pays for (the chip's instruction issue is what phase 1, phase 2 and the CRC
-// share), and two thirds of the instructions were scalar: exec-mask bookkeeping of nested branches. So the control flow is FLAT - a store that a lane does not take
-// goes to a trash byte instead of behind a branch, the length classes of an item are predicates side by side, rare kinds (raw runs, runs of a byte, an item that
-// overlaps its source) leave through one ballot-guarded block - the items of a long match come from a compacted list (a lane per long match) instead of four
-// divergent loops, a batch is cut to whole steps of 64 items, and the batch leaves LDS eight bytes per lane.
+// share), and two thirds of the instructions were scalar: exec-mask bookkeeping of nested branches. So the control flow is FLAT - the length classes of an item are
+// predicates side by side, rare kinds (raw runs, runs of a byte, an item that overlaps its source) leave through one ballot-guarded block - the items of a long match
+// come from a compacted list (a lane per long match) instead of four divergent loops, a batch is cut to whole steps of 64 items, and the batch leaves LDS eight bytes per lane.
+// Round 12: alone on the chip the kernel waits for the LDS, not for instruction issue (a third of its wave cycles were waits for LDS instructions),
+// and what an LDS instruction costs is its ACTIVE lanes: a lane that "stores" to a trash location pays like any other, and an atomic
+// whose lanes meet on one word is served lane by lane. Round 6 sent the stores a lane does not take to a trash byte / word to save the branch, and the OR into the
+// bit mask of near-item starts ran in every lane - seven in ten of them OR-ing a zero into word 0, each step of pass A. Now only the lanes that have something to
+// store take part (a mask around the store: three scalar instructions). What it bought, and what did NOT pay - one copy path of four overlapping dwords for every
+// length: fewer scalar instructions, but twice the LDS cycles of the two 8-byte pieces - is in profiles/r12_k1_resolve.txt.
 K1_KERNEL_OCC(64, 8) void lz77_groups_kernel(const uint32_t* __restrict__ pool, const uint32_t* __restrict__ tok_first, const uint32_t* __restrict__ tok_count,
                                       const BlockDesc* __restrict__ blocks, int64_t n_blocks, uint8_t* __restrict__ out_base, BlockStatus* __restrict__ status, const uint8_t* __restrict__ comp)
 {
@@ -700,11 +704,11 @@ K1_KERNEL_OCC(64, 8) void lz77_groups_kernel(const uint32_t* __restrict__ pool, 
 					const bool lmt = (t >> 31) != 0u, isl = t < K1_TOK_RAW;
 					const bool l1 = l != 0u && (lmt || isl), l2 = isl && l == 2u;
 					const uint32_t i1 = lmt ? (t >> 23) & 255u : t & 255u;
-					vb[l1 ? st : (uint32_t)P2_TRASH] = S.lit[i1];
-					vb[l2 ? st + 1u : (uint32_t)P2_TRASH] = S.lit[(t >> 8) & 255u];
+					if (l1) vb[st] = S.lit[i1];
+					if (l2) vb[st + 1u] = S.lit[(t >> 8) & 255u];
 					const bool has = n != 0u;
 					const uint32_t d = has ? st + l - n : 0u, key = item_key(t);
-					S.it[has ? ix : (uint32_t)(P2_IMAX + 7)] = d | (((n < 16u ? n : 16u) - 1u) << 11) | key;
+					if (has) S.it[ix] = d | (((n < 16u ? n : 16u) - 1u) << 11) | key;
 					const uint64_t lgm = wv::ballot(n > 16u);
 					if (lgm != 0ull)
 					{
@@ -767,9 +771,7 @@ K1_KERNEL_OCC(64, 8) void lz77_groups_kernel(const uint32_t* __restrict__ pool, 
 				q.k = !in || near ? 0u : (raw || run || len < 3u ? 4u : (len >= 9u ? 1u : (len >= 4u ? 2u : 3u)));
 				// near items: to the list
 				const uint64_t nm = wv::ballot(near);
-				const uint32_t dn = near ? d : 0u;
-				S.lg[near ? nn + wv::mbcnt(nm) : (uint32_t)(2 * P2_LONG + 7)] = q.w;
-				wv::lds_or32(&S.ib[2 * (dn >> 5)], near ? 1u << (dn & 31u) : 0u);
+				if (near) { S.lg[nn + wv::mbcnt(nm)] = q.w; wv::lds_or32(&S.ib[2 * (d >> 5)], 1u << (d & 31u)); }
 				nn += wv::popc64(nm);
 				// far items: the loads (a run's byte: one dword)
 				const uint32_t a = P + (uint32_t)src;
@@ -864,12 +866,11 @@ K1_KERNEL_OCC(64, 8) void lz77_groups_kernel(const uint32_t* __restrict__ pool, 
 				const bool c9 = len >= 9u, c4 = len >= 4u && len < 9u, c3 = len == 3u;
 				uint32_t x = idx >= nn ? 0u : (run || dist < len ? 4u : 2u);   // 0 done, 2 near item of two pieces, 4 near item of a rare kind (a run of a byte, an item that overlaps its own source)
 				const bool any4 = wv::ballot(x == 4u) != 0ull;                 // (wave-uniform: the rounds of a step without such an item do not look for one)
-				for (;;)
+				uint64_t open = wv::ballot(x != 0u);
+				while (open != 0ull)   // (whether another round is needed is known at the end of a round: no trip that only finds nothing open)
 				{
 					if (lane == 0) K1_STAT(6);
-					K1_WSTAT(15);
-					const uint64_t open = wv::ballot(x != 0u);
-					if (open == 0ull) break;
+					K1_WSTAT(15);   // (since round 12 a ROUND THAT COPIES: until round 11 the loop's last trip, which only found nothing open, was counted too - one more per near step)
 					const bool free = (open & dep) == 0ull;   // the lane's source is complete
 					if (any4)
 					{
@@ -891,6 +892,7 @@ K1_KERNEL_OCC(64, 8) void lz77_groups_kernel(const uint32_t* __restrict__ pool, 
 					if (g && c3) { const uint32_t u = wv::lds_load32u(ps); wv::lds_store16u(pd, u); pd[2] = (uint8_t)(u >> 16); }
 					x = free ? 0u : x;
 					wv::barrier();
+					open = wv::ballot(x != 0u);
 				}
 			}
 			// ---- the batch leaves for HBM: eight bytes per lane and store, the last 1..7 bytes one by one ----
