@@ -4,8 +4,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
-#define __device__
-#define __forceinline__ inline
+#include "device_on_cpu.h"
 #include "../../ngs-bits_amd/csrc/baseq_bits.h"
 
 using namespace ngsqc;

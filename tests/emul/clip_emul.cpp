@@ -5,8 +5,7 @@
 #include <cstdint>
 #include <cstring>
 #define NGSQC_REC_ON_CPU
-#define __device__
-#define __forceinline__ inline
+#include "device_on_cpu.h"
 #include "../../ngs-bits_amd/csrc/clip_visit.h"
 
 using namespace ngsqc;

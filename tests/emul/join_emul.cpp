@@ -12,11 +12,7 @@
 #include <numeric>
 #include <vector>
 #define NGSQC_REC_ON_CPU
-#define __device__
-#define __forceinline__ inline
-#ifndef __restrict__
-#define __restrict__
-#endif
+#include "device_on_cpu.h"
 static inline unsigned long long atomicAdd(unsigned long long* p, unsigned long long v) { const unsigned long long o = *p; *p += v; return o; }
 #include "join_visit.h"
 

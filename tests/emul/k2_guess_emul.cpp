@@ -4,9 +4,7 @@
 #include <cstdint>
 #include <cstring>
 #define NGSQC_K2_GUESS_ON_CPU
-#define __device__
-#define __forceinline__ inline
-#define __noinline__
+#include "device_on_cpu.h"
 static inline uint32_t __builtin_amdgcn_alignbit(uint32_t hi, uint32_t lo, uint32_t shift) { return (uint32_t)((((uint64_t)hi << 32) | lo) >> (shift & 31u)); }   // v_alignbit_b32
 #include "../../ngs-bits_amd/csrc/k2_guess.h"
 

@@ -7,12 +7,7 @@
 #include <cstring>
 #include <vector>
 #define NGSQC_REC_ON_CPU
-#define __device__
-#define __forceinline__ inline
-#define __constant__ static const
-#ifndef __restrict__
-#define __restrict__
-#endif
+#include "device_on_cpu.h"
 static inline unsigned long long atomicAdd(unsigned long long* p, unsigned long long v) { const unsigned long long o = *p; *p += v; return o; }
 namespace ngsqc { using std::max; using std::min; }
 #include "tofastq_visit.h"

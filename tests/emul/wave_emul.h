@@ -22,9 +22,7 @@
 #define K1_DEV inline
 #define K1_STAT(i) (++::ngsqc::wv::emu_stats()[i])   // instrumentation of the kernels (compiled out in the library)
 #define K1_WSTAT(i) (++::ngsqc::wv::emu().whit[i][::ngsqc::wv::emu().cur])   // wave-level count of a code region: per stretch between two rendezvous the MAXIMUM over the lanes (what a lockstep wave executes)
-#ifndef __restrict__
-#define __restrict__
-#endif
+#include "device_on_cpu.h"
 
 namespace ngsqc { namespace wv {
 

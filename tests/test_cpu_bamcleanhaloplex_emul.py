@@ -4,28 +4,22 @@ two kernels split the work at HX_LANE_OPS, and the flag bytes of the written rec
 tests/golden/ref_in. Plain integer code: held here without a GPU."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import bamcleanhaloplex_oracle as O
+import emul_build
 import haloplex_cases as K
 from conftest import ROOT
 
-EMUL = os.path.join(ROOT, "tests", "emul")
-CSRC = os.path.join(ROOT, "ngs-bits_amd", "csrc")
 GI = os.path.join(ROOT, "tests", "golden", "ref_in")
 GOLDEN = sorted(os.path.relpath(os.path.join(d, f), GI) for d, _, fs in os.walk(GI) for f in fs if f.endswith(".bam"))
 
 
 @pytest.fixture(scope="module")
 def lib():
-    so = os.path.join(EMUL, "libhaloplex.so")
-    srcs = [os.path.join(EMUL, "haloplex_emul.cpp"), os.path.join(CSRC, "haloplex_visit.h"), os.path.join(CSRC, "rec.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-Wall", "-Wno-unknown-pragmas", "-Wno-unused-function", "-o", so, srcs[0]])
-    L = C.CDLL(so)
+    L = C.CDLL(emul_build.library("haloplex_emul.cpp"))
     L.haloplex_lane_ops.restype = C.c_int32
     L.haloplex_emul.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     return L

@@ -4,17 +4,15 @@ with '+' placeholders, the one-pass soft-clip rewrite against the per-base matri
 every mode and on a seeded random family. Plain integer code: held here without a GPU."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import bamclipoverlap_oracle as O
 import clip_cases as K
+import emul_build
 from conftest import ROOT
 
-EMUL = os.path.join(ROOT, "tests", "emul")
-CSRC = os.path.join(ROOT, "ngs-bits_amd", "csrc")
 HEADER = O.read_bam(K.bam_bytes([], K.REFS))[0]
 ALL_MODES = [(m, ii) for m in (0, O.MAPQ, O.REMOVE, O.BASEQ, O.BASEN) for ii in (False, True)]
 SEED_PAIR = K.pair("seed", (K.F1, 100, "30M"), (K.R2, 110, "30M"))   # one clipped pair in front: reads_clipped is 2 at the pair behind it
@@ -22,11 +20,7 @@ SEED_PAIR = K.pair("seed", (K.F1, 100, "30M"), (K.R2, 110, "30M"))   # one clipp
 
 @pytest.fixture(scope="module")
 def lib():
-    so = os.path.join(EMUL, "libclip.so")
-    srcs = [os.path.join(EMUL, "clip_emul.cpp"), os.path.join(CSRC, "clip_visit.h"), os.path.join(CSRC, "rec.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-Wall", "-Wno-unknown-pragmas", "-Wno-unused-function", "-o", so, srcs[0]])
-    L = C.CDLL(so)
+    L = C.CDLL(emul_build.library("clip_emul.cpp"))
     L.clip_emul_pair.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]
     L.clip_emul_joins.argtypes = [C.c_char_p]
     L.clip_emul_soft_clip.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]

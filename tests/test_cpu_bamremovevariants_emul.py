@@ -3,28 +3,22 @@ of BamRemoveVariants) on the CPU, against the Python restatement: the verdict by
 BAM (tests/rmvar_cases.py) and on the reference's fixture with lines picked from its own reads. Plain integer code: held here without a GPU."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import bamremovevariants_oracle as R
+import emul_build
 import rmvar_cases as K
 from conftest import ROOT
 
 ngsqc = __import__("importlib").import_module("ngs-bits_amd")
-EMUL = os.path.join(ROOT, "tests", "emul")
-CSRC = os.path.join(ROOT, "ngs-bits_amd", "csrc")
 IN1 = os.path.join(ROOT, "tests", "golden", "ref_in", "BamRemoveVariants", "BamRemoveVariants_in1.bam")
 
 
 @pytest.fixture(scope="module")
 def lib():
-    so = os.path.join(EMUL, "librmvar.so")
-    srcs = [os.path.join(EMUL, "rmvar_emul.cpp"), os.path.join(CSRC, "rmvar_visit.h"), os.path.join(CSRC, "rec.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-Wall", "-Wno-unknown-pragmas", "-Wno-unused-function", "-o", so, srcs[0]])
-    L = C.CDLL(so)
+    L = C.CDLL(emul_build.library("rmvar_emul.cpp"))
     L.rmvar_emul.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     return L
 

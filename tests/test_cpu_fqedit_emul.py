@@ -3,31 +3,24 @@ against the Python model (tests/fqedit_oracle.py): the plan and the output text 
 the first failing entry of FastqExtract's validation, the entries of a feed that is not the last, and the same text as a stand-alone program under
 AddressSanitizer and UBSan."""
 import ctypes as C
-import os
 import subprocess
 
 import numpy as np
 import pytest
 
+import emul_build
 import fqedit_cases as K
 import fqedit_oracle as M
-from conftest import ROOT
 from test_cpu_fastqtools import REF_TESTS, ids_of, inputs, ref_run
 from test_cpu_seqpurge_emul import prepared
 
-EMUL = os.path.join(ROOT, "tests", "emul")
-CSRC = os.path.join(ROOT, "ngs-bits_amd", "csrc")
 NO_ERROR = (1 << 64) - 1
 OPS = {"trim": 0, "extract": 1, "umi": 2, "convert": 3}
 
 
 @pytest.fixture(scope="module")
 def lib():
-    so = os.path.join(EMUL, "libfqedit.so")
-    srcs = [os.path.join(EMUL, "fqedit_emul.cpp"), os.path.join(CSRC, "fqedit_visit.h"), os.path.join(CSRC, "fastq_visit.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-Wall", "-Wno-unknown-pragmas", "-Wno-unused-function", "-o", so, srcs[0]])
-    L = C.CDLL(so)
+    L = C.CDLL(emul_build.library("fqedit_emul.cpp"))
     L.fqedit_emul.restype = C.c_int32
     L.fqedit_emul.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_char_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]
     L.fqedit_format.restype = C.c_int64
@@ -119,8 +112,7 @@ def test_stand_alone_under_sanitizers(tmp_path):
     """the same text as a program of its own, built with AddressSanitizer and UBSan, over every group of the catalogue, the big entry and the designed errors:
     the texts lie in heap buffers of exactly their size and every output text in a buffer of exactly the size the plan announces, so a read outside a line or a
     write behind an entry ends the run; its plan equals the model's"""
-    exe = str(tmp_path / "fqedit_emul_main")
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wno-unknown-pragmas", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-o", exe, os.path.join(EMUL, "fqedit_emul_main.cpp")])
+    exe = emul_build.program("fqedit_emul_main.cpp", tmp_path, sanitize=True)
 
     def run(op, kw, t1, t2, ids):
         (tmp_path / "t1").write_bytes(prepared(t1, True))

@@ -4,7 +4,6 @@ that zlib accepts, 258 as 284 + 31, dictated header run-length codings, block se
 damaged stream per check of the decoder. zlib judges the catalogue; the kernels' text runs under the wave emulator (tests/emul) in five launch shapes, with
 every phase-1 case at all 16 alignments of its payload, and once more as a stand-alone program built with -fsanitize=address,undefined: there every member
 but the page-end ones, of which it takes every 40th (sanitized_batches). No GPU needed; the same catalogue on the device: tests/test_gpu_inflate_designed.py."""
-import os
 import struct
 import subprocess
 import zlib
@@ -12,8 +11,9 @@ import zlib
 import pytest
 
 import deflate_build as B
+import emul_build
 import inflate_cases as IC
-from test_k1_emul import EMUL, emul, run   # noqa: F401  (emul: the fixture that builds libk1emul.so)
+from test_k1_emul import emul, run   # noqa: F401  (emul: the fixture that builds libk1.so)
 
 VARIANTS = {"library_pool": {}, "worst_case_pool": dict(tok_mode=1), "no_parking": dict(park=0), "park_all": dict(park=64), "file_order": dict(order=0)}
 
@@ -177,14 +177,7 @@ def test_sanitized_stand_alone_run(emul, tmp_path):
     """the emulator as a program of its own under AddressSanitizer and UndefinedBehaviorSanitizer (nothing is loaded into python) on the members of
     sanitized_batches(): exit status 0, the statuses of the shared library, the same bytes.
     (Before its Kraft sums were written without a shift of a negative value this run ended in CodeShape::add: "left shift of negative value".)"""
-    exe, obj = str(tmp_path / "k1_emul_main"), str(tmp_path / "k1_emul_main.o")
-    flags = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wno-unknown-pragmas", *flags, "-c", "-o", obj, os.path.join(EMUL, "k1_emul_main.cpp")])
-    # (the sanitizers' runtimes linked statically: the program then starts whatever else the environment preloads into it, where a shared
-    # AddressSanitizer runtime refuses to run unless it comes first in the list of libraries)
-    p = subprocess.run(["g++", *flags, "-static-libasan", "-static-libubsan", "-o", exe, obj], capture_output=True, text=True)
-    if p.returncode != 0:
-        pytest.skip("the sanitized program compiles but does not link here: " + (p.stderr.strip().splitlines() or ["?"])[-1])
+    exe = emul_build.program("k1_emul_main.cpp", tmp_path, sanitize=True)
     batches = sanitized_batches()
     procs = []
     for b, (members, _) in enumerate(batches):   # the batches side by side, each a process of its own

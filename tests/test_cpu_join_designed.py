@@ -17,19 +17,14 @@ import pytest
 import bamdownsample_oracle as D
 import bamfilter_oracle as F
 import bamtofastq_oracle as Q
+import emul_build
 import join_cases as K
 from conftest import ROOT
 
-EMUL = os.path.join(ROOT, "tests", "emul")
 CSRC = os.path.join(ROOT, "ngs-bits_amd", "csrc")
 GI = os.path.join(ROOT, "tests", "golden", "ref_in")
 BITS = (2, 4, 63)
 TOOLS = ("filter", "downsample", "tofastq")
-
-
-def build(so, include_dir):
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-Wall", "-Wno-unknown-pragmas", "-Wno-unused-function", "-I", include_dir, "-o", so,
-                           os.path.join(EMUL, "join_emul.cpp")])
 
 
 def load(so):
@@ -46,11 +41,7 @@ def load(so):
 
 @pytest.fixture(scope="module")
 def lib():
-    so = os.path.join(EMUL, "libjoin.so")
-    srcs = [os.path.join(EMUL, "join_emul.cpp"), os.path.join(CSRC, "join_visit.h"), os.path.join(CSRC, "rec.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
-        build(so, CSRC)
-    return load(so)
+    return load(emul_build.library("join_emul.cpp", include=[CSRC]))
 
 
 @pytest.fixture(scope="module")
@@ -196,9 +187,7 @@ def test_golden_names_hold_no_nul():
 def test_stand_alone_under_sanitizers(tmp_path, lib, cases):
     """the same driver as a program of its own under AddressSanitizer and UBSan: tiles, pools and inputs in heap buffers of exactly their size, freed when the
     device would reuse them; its output equals the library's"""
-    exe = str(tmp_path / "join_emul_main")
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wno-unknown-pragmas", "-Wno-unused-function", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-I", CSRC, "-o", exe, os.path.join(EMUL, "join_emul_main.cpp")])
+    exe = emul_build.program("join_emul_main.cpp", tmp_path, include=[CSRC], sanitize=True)
     for case in cases.values():
         for tool in ("filter", "tofastq"):
             blob, off, tiles, part, ok, _ = inputs(case, tool)
@@ -229,9 +218,7 @@ def test_mutations_are_caught(tmp_path, cases):
         assert text.count(old) == 1, label
         (d / "join_visit.h").write_text(text.replace(old, new))
         shutil.copy(os.path.join(CSRC, "rec.h"), d / "rec.h")
-        so = str(d / "libjoin_mut.so")
-        build(so, str(d))
-        L = load(so)
+        L = load(emul_build.library("join_emul.cpp", d / "libjoin_mut.so", include=[d]))
         caught = {name for name, case in cases.items() if differences(L, case)}
         table[label] = sorted(caught)
         assert must <= caught, (label, sorted(caught))

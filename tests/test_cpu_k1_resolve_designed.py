@@ -11,7 +11,7 @@ import pytest
 import deflate_build as B
 import k1_resolve_cases as KC
 from test_cpu_inflate_designed import check_named, layout, valid_members
-from test_k1_emul import emul, run   # noqa: F401  (emul: the fixture that builds libk1emul.so)
+from test_k1_emul import emul, run   # noqa: F401  (emul: the fixture that builds libk1.so)
 
 VARIANTS = {"library_pool": {}, "worst_case_pool": dict(tok_mode=1), "three_resolver_waves": dict(p2=3), "file_order_no_parking": dict(order=0, park=0)}
 

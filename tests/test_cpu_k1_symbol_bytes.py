@@ -17,7 +17,7 @@ import pytest
 import deflate_build as B
 from inflate_cases import DL30, Member
 from test_cpu_inflate_designed import check_named, layout, valid_members
-from test_k1_emul import emul, run   # noqa: F401  (emul: the fixture that builds libk1emul.so)
+from test_k1_emul import emul, run   # noqa: F401  (emul: the fixture that builds libk1.so)
 
 LL286 = [8] * 226 + [9] * 60          # a complete code over all 286 literal/length symbols (inflate_cases._every_symbol)
 PLACES = (0, 1, 2)                    # literals in front of every match of a member

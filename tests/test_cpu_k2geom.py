@@ -6,17 +6,16 @@ import ctypes as C
 import os
 import re
 import struct
-import subprocess
 
 import numpy as np
 import pytest
 
+import emul_build
 import k2geom_cases as K
 import oracle_lib as O
 from conftest import ROOT
 
 CSRC = os.path.join(ROOT, "ngs-bits_amd", "csrc")
-EMUL = os.path.join(ROOT, "tests", "emul")
 KSH = (0, 1, 2, 3)
 
 
@@ -246,11 +245,7 @@ def test_premise_carry(name):
 # ---- K2's guess on the aligned cases ----
 @pytest.fixture(scope="module")
 def guess():
-    so = os.path.join(EMUL, "libk2guess.so")
-    srcs = [os.path.join(EMUL, "k2_guess_emul.cpp"), os.path.join(CSRC, "k2_guess.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-Wall", "-Wno-unknown-pragmas", "-o", so, srcs[0]])
-    L = C.CDLL(so)
+    L = C.CDLL(emul_build.library("k2_guess_emul.cpp"))
     L.k2_guess_first.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
     return L
 

@@ -6,19 +6,18 @@ tricks of baseq_tile_kernel (ngs-bits_amd/csrc/baseq_bits.h) on the CPU, exhaust
     (advbam.SEQ_STAR_OOB: the reference reads past the qualities there). The tools merge touching lines; the concatenated depth stays what it was.
   * tests/hand_vectors.py: depths written out by hand from the reference's lines.
   * the premises of the cases: each case still reaches what it was built to reach."""
-import os
 import subprocess
 
 import numpy as np
 import pytest
 
 import advbam as A
+import emul_build
 import hand_vectors as HV
 import hostprep as H
 import oracle_lib as O
 import readdepth_cases as RC
 import readdepth_model as RM
-from conftest import ROOT
 
 SORTED = [n for n in RC.NAMES if RC.case(n).is_sorted]
 COUNT_CASES = ("region_cuts", "cache_moves", "filters")
@@ -106,9 +105,7 @@ def test_records_survive_the_byte_form():
 def test_bit_tricks_exhaustively(tmp_path):
     """tests/emul/baseq_bits_emul.cpp: every byte value against every threshold 1..127 in every byte lane, every `left`, every range [a_lo, b_hi) of 0..256 in every
     word - the header's text compiled by g++, against the obvious loops"""
-    exe = str(tmp_path / "baseq_bits_emul")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-Wno-unknown-pragmas", "-o", exe, os.path.join(ROOT, "tests", "emul", "baseq_bits_emul.cpp")])
-    p = subprocess.run([exe], capture_output=True, text=True)
+    p = subprocess.run([emul_build.program("baseq_bits_emul.cpp", tmp_path)], capture_output=True, text=True)
     assert p.returncode == 0 and p.stdout.startswith("ok "), p.stdout + p.stderr
     counts = dict(kv.split("=") for kv in p.stdout.split()[1:])
     assert int(counts["dwords"]) >= 127 * 4 * 256 and int(counts["blocks"]) >= 127 * 65 and int(counts["words"]) >= 257 * 258 // 2

@@ -4,28 +4,22 @@ reference's five ReadQC inputs. Integer code and the reference's double division
 import ctypes as C
 import gzip
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import emul_build
 import fastq_cases as K
 import fastq_model as M
 from conftest import ROOT
 
-EMUL = os.path.join(ROOT, "tests", "emul")
-CSRC = os.path.join(ROOT, "ngs-bits_amd", "csrc")
 GI = os.path.join(ROOT, "tests", "golden", "ref_in", "ReadQC")
 NO_ERROR = (1 << 64) - 1
 
 
 @pytest.fixture(scope="module")
 def lib():
-    so = os.path.join(EMUL, "libfastqin.so")
-    srcs = [os.path.join(EMUL, "fastqin_emul.cpp"), os.path.join(CSRC, "fastq_visit.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-Wall", "-Wno-unknown-pragmas", "-Wno-unused-function", "-o", so, srcs[0]])
-    L = C.CDLL(so)
+    L = C.CDLL(emul_build.library("fastqin_emul.cpp"))
     L.fastq_block.restype = C.c_int32
     L.fastq_emul.argtypes = [C.c_char_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_uint64] + [C.c_void_p] * 3 + [C.c_int64] + [C.c_void_p] * 2
     return L

@@ -3,30 +3,23 @@ model (tests/seqpurge_oracle.py): the plan, the output text, the consensus pile-
 the reference's inputs; the table of the binomial tail against exact integers; the sweep that allows the kernel to count whole offsets; and the host's view of
 FASTQ text that the three FASTQ accumulators share (csrc/fastq_text.h), as a stand-alone program under the sanitizers."""
 import ctypes as C
-import os
 import subprocess
 
 import numpy as np
 import pytest
 
+import emul_build
 import fastq_model as F
 import purge_cases as K
 import seqpurge_oracle as M
-from conftest import ROOT
 from test_cpu_seqpurge import REF_TESTS, read_in, ref_run
 
-EMUL = os.path.join(ROOT, "tests", "emul")
-CSRC = os.path.join(ROOT, "ngs-bits_amd", "csrc")
 NO_ERROR = (1 << 64) - 1
 
 
 @pytest.fixture(scope="module")
 def lib():
-    so = os.path.join(EMUL, "libpurge.so")
-    srcs = [os.path.join(EMUL, "purge_emul.cpp"), os.path.join(CSRC, "purge_visit.h"), os.path.join(CSRC, "fastq_visit.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
-        subprocess.check_call(["g++", "-O3", "-std=c++17", "-ffp-contract=off", "-shared", "-fPIC", "-Wall", "-Wno-unknown-pragmas", "-Wno-unused-function", "-o", so, srcs[0]])
-    L = C.CDLL(so)
+    L = C.CDLL(emul_build.library("purge_emul.cpp", flags=["-O3", "-ffp-contract=off"]))
     L.purge_tail_size.restype = C.c_int32
     L.purge_tail_table.argtypes = [C.c_void_p]
     L.purge_sweep.restype = C.c_int64; L.purge_sweep.argtypes = [C.c_double]
@@ -145,9 +138,7 @@ def test_whole_counts_give_the_early_exit_verdict(lib, match_perc):
 def test_stand_alone_under_sanitizers(tmp_path):
     """the same text as a program of its own, built with AddressSanitizer and UBSan, over every group of the catalogue and the designed errors: the texts lie in
     heap buffers of exactly their size, so a read or write outside a read, a plane or a table ends the run; its plan equals the model's"""
-    exe = str(tmp_path / "purge_emul_main")
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-Wno-unknown-pragmas", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-o", exe, os.path.join(EMUL, "purge_emul_main.cpp")])
+    exe = emul_build.program("purge_emul_main.cpp", tmp_path, flags=["-ffp-contract=off"], sanitize=True)
 
     def run(t1, t2, P):
         (tmp_path / "t1").write_bytes(prepared(t1, True)); (tmp_path / "t2").write_bytes(prepared(t2, True))
@@ -197,9 +188,7 @@ def test_host_text_stand_alone_under_sanitizers(tmp_path, long_read):
     the reference's messages - as a program of its own under AddressSanitizer and UBSan: the text and the line offsets lie in heap buffers of exactly their size.
     The stripped length against parse_fastq's rule (and against prepared(), for a text in the middle of a file too), the lines against parse_fastq, the kinds
     and messages against the model of FastqEntry::validate."""
-    exe = str(tmp_path / "fastq_text_main")
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-o", exe,
-                           os.path.join(EMUL, "fastq_text_main.cpp")])
+    exe = emul_build.program("fastq_text_main.cpp", tmp_path, sanitize=True)
     for i, (_, t) in enumerate(HOST_TEXTS):
         (tmp_path / ("t%d" % i)).write_bytes(t)
     p = subprocess.run([exe, str(long_read)] + [str(tmp_path / ("t%d" % i)) for i in range(len(HOST_TEXTS))], capture_output=True, text=True)

@@ -8,6 +8,7 @@ import subprocess
 
 import pytest
 
+import emul_build
 from conftest import ROOT
 
 CSRC = os.path.join(ROOT, "ngs-bits_amd", "csrc")
@@ -72,8 +73,7 @@ def test_removed_switches_are_gone_everywhere():
 
 @pytest.fixture(scope="module")
 def dump(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("switches") / "switches_dump")
-    subprocess.check_call(["g++", "-O0", "-std=c++17", "-Wall", "-o", exe, os.path.join(ROOT, "tests", "emul", "switches_dump.cpp")])
+    exe = emul_build.program("switches_dump.cpp", tmp_path_factory.mktemp("switches"), flags=["-O0"])
 
     def run(env):
         out = subprocess.run([exe], env=env, capture_output=True, text=True, check=True).stdout

@@ -12,19 +12,14 @@ import numpy as np
 import pytest
 
 import bamtofastq_oracle as Q
+import emul_build
 import tofastq_cases as K
 from bamfilter_oracle import Rec
 from conftest import ROOT
 
-EMUL = os.path.join(ROOT, "tests", "emul")
 CSRC = os.path.join(ROOT, "ngs-bits_amd", "csrc")
 HEADERS = ("tofastq_visit.h", "join_visit.h", "rec.h")
 DENSE = 40   # entries of up to 2 * DENSE bytes meet every cut; longer ones the cuts within DENSE bytes of either end and every 251st between
-
-
-def build(so, include_dir):
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-Wall", "-Wno-unknown-pragmas", "-Wno-unused-function", "-I", include_dir, "-o", so,
-                           os.path.join(EMUL, "tofastq_emul.cpp")])
 
 
 def load(so):
@@ -37,11 +32,7 @@ def load(so):
 
 @pytest.fixture(scope="module")
 def lib():
-    so = os.path.join(EMUL, "libtofastq.so")
-    srcs = [os.path.join(EMUL, "tofastq_emul.cpp")] + [os.path.join(CSRC, h) for h in HEADERS]
-    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
-        build(so, CSRC)
-    return load(so)
+    return load(emul_build.library("tofastq_emul.cpp", include=[CSRC]))
 
 
 @pytest.fixture(scope="module")
@@ -120,9 +111,7 @@ def test_names_with_more_than_one_nul(lib):
 def test_stand_alone_under_sanitizers(tmp_path, runs):
     """the same text as a program of its own under AddressSanitizer and UBSan: every record in a heap buffer of exactly its size, every entry in one of exactly
     the announced size"""
-    exe = str(tmp_path / "tofastq_emul_main")
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wno-unknown-pragmas", "-Wno-unused-function", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-I", CSRC, "-o", exe, os.path.join(EMUL, "tofastq_emul_main.cpp")])
+    exe = emul_build.program("tofastq_emul_main.cpp", tmp_path, include=[CSRC], sanitize=True)
     for name in ("bases", "qualities_extend0", "qualities_extend12", "throws_in_tile", "region", "fix"):
         run = runs[name]
         recs = run.records
@@ -152,9 +141,7 @@ def test_mutations_are_caught(tmp_path, runs):
         (d / "tofastq_visit.h").write_text(text.replace(old, new))
         for h in HEADERS[1:]:
             shutil.copy(os.path.join(CSRC, h), d / h)
-        so = str(d / "libtofastq_mut.so")
-        build(so, str(d))
-        L = load(so)
+        L = load(emul_build.library("tofastq_emul.cpp", d / "libtofastq_mut.so", include=[d]))
         caught = {name for name, run in runs.items() if differences(L, run)}
         table[label] = sorted(caught)
         assert must <= caught, (label, sorted(caught))

@@ -9,20 +9,18 @@ import ctypes as C
 import os
 import random
 import struct
-import subprocess
 import sys
 
 import pytest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-EMUL = os.path.join(HERE, "emul")
-CSRC = os.path.join(os.path.dirname(HERE), "ngs-bits_amd", "csrc")
 GI = os.path.join(HERE, "golden", "ref_in")
 ngsqc = __import__("importlib").import_module("ngs-bits_amd")
 sys.path.insert(0, os.path.join(os.path.dirname(HERE), "oracle"))
 import cram_decode as CD  # noqa: E402
 import cram_encode as CE  # noqa: E402
 import cram_plan_ref as R  # noqa: E402
+import emul_build  # noqa: E402
 import qualgen  # noqa: E402
 from test_cpu_cram import bam_stream  # noqa: E402
 
@@ -31,11 +29,7 @@ EMU_PAGE_FAULT, EMU_GUARD_WRITTEN, EMU_PLACEMENTS_DIFFER, EMU_NO_MEMORY = 1, 2, 
 
 @pytest.fixture(scope="module")
 def emul():
-    so = os.path.join(EMUL, "libcramemul.so")
-    srcs = [os.path.join(EMUL, "cram_emul.cpp"), os.path.join(EMUL, "wave_emul.h"), os.path.join(CSRC, "cram_dev_kernels.h"), os.path.join(CSRC, "cram_plan.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-Wall", "-Wno-unknown-pragmas", "-o", so, srcs[0]])
-    L = C.CDLL(so)
+    L = C.CDLL(emul_build.library("cram_emul.cpp"))
     L.cram_emul_run.restype = C.c_int
     L.cram_emul_run.argtypes = [C.c_char_p, C.c_int64, C.c_char_p, C.c_int64, C.c_char_p, C.c_int64, C.c_char_p, C.c_int64, C.c_uint64, C.c_char_p, C.c_uint64,
                                 C.c_char_p, C.c_uint64, C.c_char_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]

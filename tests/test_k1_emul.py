@@ -5,17 +5,15 @@ GPU runs of the same kernels are tests/test_gpu_inflate.py / test_gpu_parity.py.
 import ctypes as C
 import os
 import random
-import subprocess
 import zlib
 
 import numpy as np
 import pytest
 
 import bamgen_lib
+import emul_build
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-EMUL = os.path.join(HERE, "emul")
-CSRC = os.path.join(os.path.dirname(HERE), "ngs-bits_amd", "csrc")
 
 
 class BD(C.Structure):
@@ -28,11 +26,7 @@ class BS(C.Structure):
 
 @pytest.fixture(scope="module")
 def emul():
-    so = os.path.join(EMUL, "libk1emul.so")
-    srcs = [os.path.join(EMUL, "k1_emul.cpp"), os.path.join(EMUL, "wave_emul.h"), os.path.join(CSRC, "k1_kernels.h"), os.path.join(CSRC, "k1_types.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-Wall", "-Wno-unknown-pragmas", "-o", so, srcs[0]])
-    L = C.CDLL(so)
+    L = C.CDLL(emul_build.library("k1_emul.cpp"))
     L.k1_emul_inflate.argtypes = [C.c_char_p, C.POINTER(BD), C.c_int64, C.c_void_p, C.POINTER(BS), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint64)]
     return L
 

@@ -5,27 +5,21 @@ without a GPU. BAM record layout: SAM spec 4.2; the reference reaches it through
 import ctypes as C
 import glob
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import bamgen_lib as G
+import emul_build
 import oracle_lib as O
 from conftest import ROOT
 
-EMUL = os.path.join(ROOT, "tests", "emul")
-CSRC = os.path.join(ROOT, "ngs-bits_amd", "csrc")
 GI = os.path.join(ROOT, "tests", "golden", "ref_in")
 
 
 @pytest.fixture(scope="module")
 def lib():
-    so = os.path.join(EMUL, "libk2guess.so")
-    srcs = [os.path.join(EMUL, "k2_guess_emul.cpp"), os.path.join(CSRC, "k2_guess.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-Wall", "-Wno-unknown-pragmas", "-o", so, srcs[0]])
-    L = C.CDLL(so)
+    L = C.CDLL(emul_build.library("k2_guess_emul.cpp"))
     L.k2_guess_classify.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]
     L.k2_guess_first.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
     L.k2_guess_counts.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]
