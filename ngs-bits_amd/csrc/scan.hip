@@ -166,6 +166,14 @@ __device__ __forceinline__ void bq_close(const ScanParams& p, const uint32_t* st
 	if (k < (long long)state[1] && k < p.bq_cap) p.bq_list[k] = (int64_t)BQ_HOLE;
 }
 
+// |isize| as the reference takes it (abs(al.insertSize())). INT32_MIN has no magnitude an int holds - abs() of it is undefined in the reference and would come back
+// negative here, below 1000 and an index in front of the LDS histogram: it counts as INT32_MAX, "1000 or more" and "no mate overlap" like every other huge insert.
+__device__ __forceinline__ int abs_isize(int v)
+{
+	const uint32_t u = v < 0 ? 0u - (uint32_t)v : (uint32_t)v;
+	return (int)min(u, (uint32_t)INT32_MAX);
+}
+
 // Everything after the CIGAR sums are known. ord = ordinal of the record in the file.
 template <int MODE>
 __device__ static void classify(const ScanParams& p, const RecView& r, long long ord, long long ref_len, long long clip, bool spliced, Acc& a, uint32_t* lds_hist)
@@ -297,7 +305,7 @@ __device__ static void classify(const ScanParams& p, const RecView& r, long long
 									a.v[A_NO_OVERLAP] += n;
 									diff_add(p, i, s, e);
 								}
-								int insert_size = abs(r.isize);
+								int insert_size = abs_isize(r.isize);
 								if (read1 && paired && proper && !spliced && 2 * length > insert_size)
 								{
 									int ovl = 2 * length - insert_size;
@@ -329,7 +337,7 @@ __device__ static void classify(const ScanParams& p, const RecView& r, long long
 		a.n[A_PP]++;
 		if (!spliced)
 		{
-			int insert_size = abs(r.isize);
+			int insert_size = abs_isize(r.isize);
 			if (insert_size < 1000)
 			{
 				a.n[A_INS_CNT]++; a.n[A_INS_SUM] += (uint32_t)insert_size;
