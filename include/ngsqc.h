@@ -272,10 +272,13 @@ int  ngsqc_purge_result(ngsqc_purge* p, ngsqc_purge_stats* st);
 /* without outputs: the plan rows of pairs [first, first + n) into out[n][8] */
 int  ngsqc_purge_plan(ngsqc_purge* p, int64_t first, int64_t n, int32_t* out);
 
-/* ---- the per-entry FASTQ-to-FASTQ tools: FastqTrim, FastqExtract, FastqExtractUMI, FastqConvert (src/<tool>/main.cpp). "Edit every entry of a FASTQ stream
+/* ---- the per-entry FASTQ-to-FASTQ tools: FastqTrim, FastqExtract, FastqExtractUMI, FastqConvert, FastqExtractBarcode, FastqAddBarcode, FastqDownsample,
+ * FastqConcat (src/<tool>/main.cpp). "Edit every entry of a FASTQ stream
  * and write it again": an accumulator like ngsqc_purge. The caller inflates the input and feeds its TEXT in pieces cut anywhere; FastqExtractUMI has two
  * inputs ("sides"), each with its own carry, and a feed processes the entries complete on both; the other operations have one (text2 NULL, n2 0). last != 0
- * ends the input (line structure as ngsqc_fastq); with two sides the run ends silently at the shorter one. Per entry and side the device fills a plan record
+ * ends the input (line structure as ngsqc_fastq); with two sides the run ends silently at the shorter one. An operation has one or two output STREAMS, and
+ * for the first four stream k holds the entries of side k; the table below names sides and streams of the others. last ends a FILE: a feed behind it begins
+ * the next file (FastqConcat's and FastqAddBarcode's lists), output positions and entry ordinals carry on. Per entry and stream the device fills a plan record
  * of 8 int32:
  *   [0] keep     1: the entry is written, 0: dropped (the ranges below then describe the whole lines)
  *   [1] ins_at   byte offset in the header line in front of which text is inserted
@@ -294,13 +297,21 @@ int  ngsqc_purge_plan(ngsqc_purge* p, int64_t first, int64_t n, int32_t* out);
  *                         non-empty header is validated with the kinds 1..5 of ngsqc_fastq, long_read included: the first failing entry makes feed return NGSQC_E_FORMAT
  *                         with the reference's message, and the accumulator is void from then on
  *   NGSQC_FQEDIT_UMI      cut1, cut2 (>= 0): the first cut k bytes of the bases and quality lines of read k go (a shorter line becomes empty)
- *   NGSQC_FQEDIT_CONVERT  every quality byte - 31 */
-enum { NGSQC_FQEDIT_TRIM = 0, NGSQC_FQEDIT_EXTRACT = 1, NGSQC_FQEDIT_UMI = 2, NGSQC_FQEDIT_CONVERT = 3 };
+ *   NGSQC_FQEDIT_CONVERT  every quality byte - 31
+ *   NGSQC_FQEDIT_BARCODE_CUT  one side, two streams, both from side 0; cut1 (>= 0) is the cut. Stream 1 (main): the bases and quality lines without their first
+ *                         cut bytes (a shorter line becomes empty); stream 2 (index): the first cut bytes of each line, or the bytes there are
+ *   NGSQC_FQEDIT_BARCODE_ADD  three sides (ngsqc_fqedit_feed3), two streams from sides 0 and 1: the text ":" len3 ",0:" bases3 "," - the bases line of the entry
+ *                         of side 2 and its length in decimal - goes behind the first space-delimited token of both headers, composed on the device
+ *   NGSQC_FQEDIT_DOWNSAMPLE  two sides, two streams; ngsqc_fqedit_downsample comes first. Pair r of the whole run (all feeds) is written when value r of glibc's
+ *                         rand() behind srand(seed) says so, as ngsqc_downsample_keep(seed, percentage, r, 1) does; the decisions are made on the device
+ *   NGSQC_FQEDIT_COPY     one side, one stream: every entry as it is */
+enum { NGSQC_FQEDIT_TRIM = 0, NGSQC_FQEDIT_EXTRACT = 1, NGSQC_FQEDIT_UMI = 2, NGSQC_FQEDIT_CONVERT = 3,
+       NGSQC_FQEDIT_BARCODE_CUT = 4, NGSQC_FQEDIT_BARCODE_ADD = 5, NGSQC_FQEDIT_DOWNSAMPLE = 6, NGSQC_FQEDIT_COPY = 7 };
 typedef struct ngsqc_fqedit ngsqc_fqedit;
 typedef struct ngsqc_fqedit_params {
 	int32_t op, long_read;                /* NGSQC_FQEDIT_*; long_read: qualities up to 126 are valid, and a wave per entry in the plan of EXTRACT */
 	int32_t start, end, len, max_len;     /* TRIM */
-	int32_t cut1, cut2;                   /* UMI */
+	int32_t cut1, cut2;                   /* UMI; BARCODE_CUT: cut1 */
 	int32_t invert, reserved;             /* EXTRACT: -v */
 } ngsqc_fqedit_params;
 typedef struct ngsqc_fqedit_stats {
@@ -316,12 +327,21 @@ const char* ngsqc_fqedit_last_error(const ngsqc_fqedit* e);   /* e NULL: the las
  * A later duplicate of an id replaces the earlier one; an id with length -2 is as good as not listed. The table lives in device memory, open-addressed,
  * hashed by the read-name hash of the mate join (NGSQC_NAME_HASH_BITS truncates it); a hash hit is confirmed by comparing the bytes. */
 int  ngsqc_fqedit_ids(ngsqc_fqedit* e, const void* names, const int32_t* name_len, const int32_t* lengths, int64_t n);
-/* once, before the first feed; out2 with UMI only (and then needed); compression_level 0..9 */
+/* once, before the first feed; out2 for exactly the operations with two streams (UMI, BARCODE_CUT: the index, BARCODE_ADD, DOWNSAMPLE); compression_level 0..9 */
 int  ngsqc_fqedit_outputs(ngsqc_fqedit* e, const char* out1, const char* out2, int32_t compression_level);
-int  ngsqc_fqedit_feed(ngsqc_fqedit* e, const uint8_t* text1, int64_t n1, const uint8_t* text2, int64_t n2, int32_t last);
+int  ngsqc_fqedit_feed(ngsqc_fqedit* e, const uint8_t* text1, int64_t n1, const uint8_t* text2, int64_t n2, int32_t last);   /* refuses BARCODE_ADD: it has three sides */
+/* the same with a third side; an operation with fewer sides takes NULL / 0 for the sides it does not have */
+int  ngsqc_fqedit_feed3(ngsqc_fqedit* e, const uint8_t* text1, int64_t n1, const uint8_t* text2, int64_t n2, const uint8_t* text3, int64_t n3, int32_t last);
+/* DOWNSAMPLE, once, before the first feed: the seed of srand() and the percentage of pairs to keep (NGSQC_E_ARG outside (0, 100)); want_headers != 0 keeps the
+ * header lines of side 0 of the kept pairs, gathered on the device, for ngsqc_fqedit_kept_headers */
+int  ngsqc_fqedit_downsample(ngsqc_fqedit* e, uint32_t seed, double percentage, int32_t want_headers);
+/* the entries seen on each side so far, those no partner came for included (behind the last piece of a file: every entry of every side) */
+int  ngsqc_fqedit_side_entries(const ngsqc_fqedit* e, int64_t out[3]);
+/* after ngsqc_fqedit_result: the kept header lines, each followed by "\n", n bytes in all; the text belongs to the accumulator and goes with ngsqc_fqedit_destroy */
+int  ngsqc_fqedit_kept_headers(ngsqc_fqedit* e, char** text, int64_t* n);
 /* closes the outputs (no feed may follow) and fills st (may be NULL) */
 int  ngsqc_fqedit_result(ngsqc_fqedit* e, ngsqc_fqedit_stats* st);
-/* without outputs: the plan rows of entries [first, first + n) into out[n][sides][8], sides = 2 for UMI and 1 otherwise */
+/* without outputs: the plan rows of entries [first, first + n) into out[n][streams][8], streams = 2 for UMI, BARCODE_CUT, BARCODE_ADD and DOWNSAMPLE, 1 otherwise */
 int  ngsqc_fqedit_plan(ngsqc_fqedit* e, int64_t first, int64_t n, int32_t* out);
 
 /* ---- fused job: ONE pass over the BAM for every consumer --------------------------------------------------------------------

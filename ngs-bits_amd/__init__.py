@@ -15,6 +15,6 @@ from .capi import (  # noqa: F401
     ClipError, CLIP_MAPQ, CLIP_REMOVE, CLIP_BASEQ, CLIP_BASEN, CLIP_COUNT_NAMES, CLIP_PLAN_COLUMNS, CLIPERR_NONE, CLIPERR_ORIENT, CLIPERR_CIGAR_CHAR, CLIPERR_LENGTH, CLIPERR_SC_ORDER,
     CLIPERR_SC_START, CLIPERR_SC_END, CLIPERR_SC_INDEX, CLIPERR_SC_OP, CLIPERR_BAD_BASE, CLIPERR_UNSUPPORTED,
     FastqStats, FastqReport, Purge, PurgeParams, PurgeStats, purge_plan, PURGE_PLAN_COLUMNS,
-    FastqEdit, FqEditParams, FqEditStats, fastq_edit_plan, FQEDIT_PLAN_COLUMNS, FQEDIT_OPS,
+    FastqEdit, FqEditParams, FqEditStats, fastq_edit_plan, FQEDIT_PLAN_COLUMNS, FQEDIT_OPS, FQEDIT_SHAPE,
 )
 from .dist import allreduce_counters, combine_counters_local, shard_blocks, scan_mapping_sharded, scan_mapping_sharded_local, scan_depth_sharded_local  # noqa: F401,E402

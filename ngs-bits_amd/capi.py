@@ -200,7 +200,8 @@ class FqEditStats(C.Structure):
                 ("h2d_ms", C.c_double), ("index_ms", C.c_double), ("plan_ms", C.c_double), ("format_ms", C.c_double), ("deflate_ms", C.c_double), ("wait_ms", C.c_double)]
 
 
-FQEDIT_OPS = {"trim": 0, "extract": 1, "umi": 2, "convert": 3}
+FQEDIT_OPS = {"trim": 0, "extract": 1, "umi": 2, "convert": 3, "barcode_cut": 4, "barcode_add": 5, "downsample": 6, "copy": 7}
+FQEDIT_SHAPE = {"barcode_cut": (1, 2), "barcode_add": (3, 2), "downsample": (2, 2), "umi": (2, 2)}   # (sides, streams); (1, 1) otherwise
 FQEDIT_PLAN_COLUMNS = ("keep", "ins_at", "ins_len", "b_off", "b_len", "q_off", "q_len", "q_delta")
 PURGE_PLAN_COLUMNS = ("len1_in", "len2_in", "insert_offset", "adapter_fwd", "adapter_rev", "len1_out", "len2_out", "flags")
 PURGE_A1 = b"AGATCGGAAGAGCACACGTCTGAACTCCAGTCA"
@@ -298,6 +299,10 @@ def lib():
         L.ngsqc_fqedit_feed.restype = i32; L.ngsqc_fqedit_feed.argtypes = [vp, cp, i64, cp, i64, C.c_int32]
         L.ngsqc_fqedit_result.restype = i32; L.ngsqc_fqedit_result.argtypes = [vp, C.POINTER(FqEditStats)]
         L.ngsqc_fqedit_plan.restype = i32; L.ngsqc_fqedit_plan.argtypes = [vp, i64, i64, vp]
+        L.ngsqc_fqedit_feed3.restype = i32; L.ngsqc_fqedit_feed3.argtypes = [vp, cp, i64, cp, i64, cp, i64, C.c_int32]
+        L.ngsqc_fqedit_downsample.restype = i32; L.ngsqc_fqedit_downsample.argtypes = [vp, C.c_uint32, C.c_double, C.c_int32]
+        L.ngsqc_fqedit_side_entries.restype = i32; L.ngsqc_fqedit_side_entries.argtypes = [vp, vp]
+        L.ngsqc_fqedit_kept_headers.restype = i32; L.ngsqc_fqedit_kept_headers.argtypes = [vp, C.POINTER(vp), C.POINTER(i64)]
         L.ngsqc_open_shard.restype = i32; L.ngsqc_open_shard.argtypes = [cp, i32, i32, i32, C.POINTER(vp)]
         L.ngsqc_open_memory_shard.restype = i32; L.ngsqc_open_memory_shard.argtypes = [vp, C.c_size_t, i32, i32, i32, C.POINTER(vp)]
         L.ngsqc_comm_unique_id.restype = i32; L.ngsqc_comm_unique_id.argtypes = [vp]
@@ -373,6 +378,7 @@ EXPORTS = [
     "ngsqc_fastq_create", "ngsqc_fastq_destroy", "ngsqc_fastq_last_error", "ngsqc_fastq_feed", "ngsqc_fastq_result", "ngsqc_fastq_length_hist", "ngsqc_fastq_cycle_stats",
     "ngsqc_purge_create", "ngsqc_purge_destroy", "ngsqc_purge_last_error", "ngsqc_purge_outputs", "ngsqc_purge_file_names", "ngsqc_purge_feed", "ngsqc_purge_result", "ngsqc_purge_plan",
     "ngsqc_fqedit_create", "ngsqc_fqedit_destroy", "ngsqc_fqedit_last_error", "ngsqc_fqedit_ids", "ngsqc_fqedit_outputs", "ngsqc_fqedit_feed", "ngsqc_fqedit_result", "ngsqc_fqedit_plan",
+    "ngsqc_fqedit_feed3", "ngsqc_fqedit_downsample", "ngsqc_fqedit_side_entries", "ngsqc_fqedit_kept_headers",
 ]
 
 
@@ -1085,19 +1091,30 @@ def purge_plan(text1, text2, device=0, **params):
 
 
 class FastqEdit:
-    """The per-entry FASTQ-to-FASTQ tools on the device (include/ngsqc.h ngsqc_fqedit_*). op: "trim", "extract", "umi" or "convert". feed() takes the text in pieces
-    cut anywhere (two texts for "umi"), result() closes the outputs and returns the statistics as a dict and sets .stats. Without outputs the plan is kept:
-    plan() returns (n, 8) int32 (FQEDIT_PLAN_COLUMNS), (n, 2, 8) for "umi". A failing entry of "extract" raises NgsqcError (code -2) with the reference's
-    message; .error then holds (entry, kind)."""
+    """The per-entry FASTQ-to-FASTQ tools on the device (include/ngsqc.h ngsqc_fqedit_*). op: "trim", "extract", "umi", "convert", "barcode_cut" (the cut is
+    cut1), "barcode_add" (three texts), "downsample" (with seed, percentage, want_headers) or "copy". feed() takes the text in pieces
+    cut anywhere (two texts for "umi" and "downsample"), result() closes the outputs and returns the statistics as a dict and sets .stats. Without outputs the plan is kept:
+    plan() returns (n, 8) int32 (FQEDIT_PLAN_COLUMNS), (n, 2, 8) for an op with two output streams (.streams). A failing entry of "extract" raises NgsqcError
+    (code -2) with the reference's message; .error then holds (entry, kind)."""
 
-    def __init__(self, op, device=0, long_read=False, start=0, end=0, len=0, max_len=0, cut1=0, cut2=0, invert=False):
+    def __init__(self, op, device=0, long_read=False, start=0, end=0, len=0, max_len=0, cut1=0, cut2=0, invert=False, seed=None, percentage=None, want_headers=False):
         self.h = C.c_void_p()
         self.stats, self.error = None, None
-        self.sides = 2 if op == "umi" else 1
+        self.sides, self.streams = FQEDIT_SHAPE.get(op, (1, 1))
         p = FqEditParams(FQEDIT_OPS[op], int(bool(long_read)), int(start), int(end), int(len), int(max_len), int(cut1), int(cut2), int(bool(invert)), 0)
         rc = lib().ngsqc_fqedit_create(int(device), C.byref(p), C.byref(self.h))
         if rc != 0:
             raise NgsqcError(rc, (lib().ngsqc_fqedit_last_error(None) or b"").decode("latin-1"))
+        if seed is not None or percentage is not None or want_headers:
+            try:
+                self.downsample(1 if seed is None else seed, percentage, want_headers)
+            except NgsqcError:
+                self.close()
+                raise
+
+    def downsample(self, seed, percentage, want_headers=False):
+        """op "downsample", once, before the first feed (the constructor calls it when it is given seed, percentage or want_headers)"""
+        self._chk(lib().ngsqc_fqedit_downsample(self.h, int(seed) & 0xFFFFFFFF, float("nan") if percentage is None else float(percentage), int(bool(want_headers))))
 
     def close(self):
         if getattr(self, "h", None):
@@ -1124,9 +1141,25 @@ class FastqEdit:
     def outputs(self, out1, out2=None, compression_level=1):
         self._chk(lib().ngsqc_fqedit_outputs(self.h, os.fsencode(out1), None if out2 is None else os.fsencode(out2), int(compression_level)))
 
-    def feed(self, text1, text2=None, last=False):
+    def feed(self, text1, text2=None, text3=None, last=False):
         text1 = bytes(text1); text2 = None if text2 is None else bytes(text2)
-        self._chk(lib().ngsqc_fqedit_feed(self.h, text1, len(text1), text2, 0 if text2 is None else len(text2), int(bool(last))))
+        if text3 is None:
+            self._chk(lib().ngsqc_fqedit_feed(self.h, text1, len(text1), text2, 0 if text2 is None else len(text2), int(bool(last))))
+        else:
+            text3 = bytes(text3)
+            self._chk(lib().ngsqc_fqedit_feed3(self.h, text1, len(text1), text2, 0 if text2 is None else len(text2), text3, len(text3), int(bool(last))))
+
+    def side_entries(self):
+        """the entries seen on each side so far, those no partner came for included"""
+        out = np.zeros(3, dtype=np.int64)
+        self._chk(lib().ngsqc_fqedit_side_entries(self.h, out.ctypes.data))
+        return [int(v) for v in out[:self.sides]]
+
+    def kept_headers(self):
+        """after result(), with want_headers: the header lines of read 1 of the kept pairs, each followed by a line feed, as bytes"""
+        p, n = C.c_void_p(), C.c_int64(0)
+        self._chk(lib().ngsqc_fqedit_kept_headers(self.h, C.byref(p), C.byref(n)))
+        return C.string_at(p, n.value) if n.value else b""
 
     def result(self):
         st = FqEditStats()
@@ -1138,19 +1171,19 @@ class FastqEdit:
     def plan(self, first=0, n=None):
         if n is None:
             n = self.result()["entries"] - first
-        out = np.zeros((max(int(n), 1), self.sides, 8), dtype=np.int32)
+        out = np.zeros((max(int(n), 1), self.streams, 8), dtype=np.int32)
         self._chk(lib().ngsqc_fqedit_plan(self.h, int(first), int(n), out.ctypes.data))
-        return out[:int(n)] if self.sides == 2 else out[:int(n), 0]
+        return out[:int(n)] if self.streams == 2 else out[:int(n), 0]
 
 
-def fastq_edit_plan(text1, text2=None, device=0, ids=None, **params):
-    """The plan of a per-entry FASTQ tool alone for whole FASTQ texts: (n, 8) int32, a row per entry (FQEDIT_PLAN_COLUMNS); (n, 2, 8) with two texts. No file is
-    written. params: op and the parameters of FastqEdit; ids: (names, lengths) for "extract"."""
+def fastq_edit_plan(text1, text2=None, device=0, ids=None, text3=None, **params):
+    """The plan of a per-entry FASTQ tool alone for whole FASTQ texts: (n, 8) int32, a row per entry (FQEDIT_PLAN_COLUMNS); (n, 2, 8) for an op with two output
+    streams. No file is written. params: op and the parameters of FastqEdit; ids: (names, lengths) for "extract"; text3: the barcode reads of "barcode_add"."""
     e = FastqEdit(device=device, **params)
     try:
         if ids is not None:
             e.ids(*ids)
-        e.feed(text1, text2, last=True)
+        e.feed(text1, text2, text3, last=True)
         return e.plan()
     finally:
         e.close()

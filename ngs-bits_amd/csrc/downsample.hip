@@ -19,6 +19,7 @@
 // moves from one boundary to the next with the jump for CHUNK steps (31 x 31 multiply-adds: about a quarter of one per decision); on the device one lane
 // walks one chunk with the 31-word ring in registers.
 #include "recwrite.h"
+#include "keep_stream.h"
 
 namespace ngsqc {
 
@@ -236,6 +237,16 @@ bool percentage_ok(double p) { return p > 0 && p < 100; }
 } // namespace
 
 namespace lib {
+// keep_stream.h: the generator for ngsqc_fqedit (FastqDownsample)
+struct KeepStream { KeepGen gen; KeepStream(const char* t, uint32_t seed, double p) : gen(t, seed, p, 0) {} };
+KeepStream* keep_stream_open(const char* tool, uint32_t seed, double percentage)
+{
+	if (!percentage_ok(percentage)) { char b[64]; snprintf(b, sizeof(b), "%g", percentage); throw ArgError(std::string("Invalid percentage ") + b + "!"); }
+	return new KeepStream(tool, seed, percentage);
+}
+const uint8_t* keep_stream_run(KeepStream* k, int64_t k0, int64_t m, hipStream_t s) { const int64_t base = k->gen.run(k0, m, s); return (const uint8_t*)k->gen.keep.p + (k0 - base); }
+void keep_stream_close(KeepStream* k) { delete k; }
+
 void downsample(ngsqc_handle* h, const ngsqc_downsample_params* dp, const char* out_path, ngsqc_downsample_counts* cnt, char** kept_names)
 {
 	if (kept_names) *kept_names = nullptr;

@@ -1,5 +1,5 @@
 // The input side of the accumulators that take FASTQ text in pieces cut anywhere and write FASTQ again (ngsqc_purge in purge.hip, ngsqc_fqedit in fqedit.hip;
-// their output side is fastq_outputs.h): FastqFeed - the text of one or two sides, its carry, the line index on the device (launch_fastq_line_index of
+// their output side is fastq_outputs.h): FastqFeed - the text of one, two or three sides, its carry, the line index on the device (launch_fastq_line_index of
 // fastqin.hip) and the entries of a feed. The plan kernels, the statistics and what a surplus on one side means stay with the caller; nothing here asks who
 // calls. ngsqc_fastq (fastqin.hip) keeps its own pipeline of two pinned slots and takes fastq_text.h, fq_fetch_entry and fastq_guard only - which is why this
 // header needs handle.h alone: join.h's kernels and rocPRIM in fastqin.hip's code object made the first line index of a process 6 to 8 ms slower.
@@ -37,13 +37,14 @@ struct FastqFeed
 		std::vector<uint8_t> text;   // the carry, then what was fed
 		size_t n_idx = 0; int64_t blocks = 0; unsigned long long L = 0, E = 0;   // of the last feed: bytes indexed, their blocks, their lines, the entries they make
 		DevBuf<uint8_t> d_text, d_tmp; DevBuf<uint32_t> d_cnt, d_lines; DevBuf<int64_t> d_base;
-	} side[2];
+	} side[3];
 
 	void open(int dev, int n_sides)
 	{
 		int n_dev = 0;
 		if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) throw std::runtime_error("no HIP device available (libngsqc_hip has no CPU fallback)");
 		if (dev < 0 || dev >= n_dev) throw ArgError("no such device");
+		if (n_sides < 1 || n_sides > 3) throw ArgError("a FASTQ feed has one to three sides");
 		device = dev; sides = n_sides;
 		HIPCHK(hipSetDevice(device));
 		HIPCHK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
@@ -57,8 +58,9 @@ struct FastqFeed
 	}
 	// The pieces go behind the carries; every side is uploaded and indexed. Returns the entries complete on every side (entry r is lines 4r .. 4r + 3 of
 	// side k in side[k].d_text / d_lines, side[k].L lines), or -1 when no line ends in these pieces: nothing new can be complete, nothing was indexed and
-	// there is no carry to cut. who: the entry point, for the message.
-	int64_t feed(const char* who, const uint8_t* const tx[2], const int64_t nn[2], bool last, double& h2d_ms, double& index_ms, double& wait_ms)
+	// there is no carry to cut. who: the entry point, for the message. tx, nn: one per side. Behind the last piece the file has ended: the carries are empty,
+	// the line phase starts again, and a further feed begins the next file.
+	int64_t feed(const char* who, const uint8_t* const* tx, const int64_t* nn, bool last, double& h2d_ms, double& index_ms, double& wait_ms)
 	{
 		bool any_newline = false;
 		for (int k = 0; k < sides; ++k)
@@ -82,7 +84,7 @@ struct FastqFeed
 		HIPCHK(hipEventRecord(ev[1], stream));
 		for (int k = 0; k < sides; ++k) { Side& s = side[k]; launch_fastq_line_index(s.d_text.p, s.n_idx, s.d_cnt.p, s.d_base.p, s.d_tmp.p, s.d_lines.p, stream); }
 		HIPCHK(hipEventRecord(ev[2], stream));
-		int64_t tot[2] = {0, 0};
+		int64_t tot[3] = {0, 0, 0};
 		for (int k = 0; k < sides; ++k) HIPCHK(hipMemcpyAsync(&tot[k], side[k].d_base.p + side[k].blocks, 8, hipMemcpyDeviceToHost, stream));
 		const double w0 = wall_ms();
 		HIPCHK(hipStreamSynchronize(stream));
@@ -91,7 +93,9 @@ struct FastqFeed
 		float ms = 0;
 		HIPCHK(hipEventElapsedTime(&ms, ev[0], ev[1])); h2d_ms += ms;
 		HIPCHK(hipEventElapsedTime(&ms, ev[1], ev[2])); index_ms += ms;
-		return (int64_t)(sides == 2 ? std::min(side[0].E, side[1].E) : side[0].E);
+		unsigned long long n = side[0].E;
+		for (int k = 1; k < sides; ++k) n = std::min(n, side[k].E);
+		return (int64_t)n;
 	}
 	// The carry behind the n entries the feed gave: what lies behind line 4n - 1 stays as the side's text, nothing behind the last piece. Bit k of the result: side k
 	// holds at least one more line. Behind the last piece that is text the caller has to decide about: the empty lines at the end are stripped, so the last line of
