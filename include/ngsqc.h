@@ -592,8 +592,8 @@ int ngsqc_csi_assemble(const char* csi_path, int32_t min_shift, int32_t depth, i
 
 typedef struct ngsqc_shard_summary {
 	int64_t n_records;         /* records owned by the shard */
-	int64_t first_abs;         /* inflated-stream offset (whole file) of the first record owned; -1: no record starts in the shard */
-	int64_t exit_abs;          /* offset of the first record behind the shard (= the next shard's first_abs); -1 with first_abs */
+	int64_t first_abs;         /* inflated-stream offset (whole file) of the first record owned; -1: the shard owns no record (none starts in its own members) */
+	int64_t exit_abs;          /* offset of the first record behind the shard (= the first_abs of the next shard that owns one); -1 with first_abs */
 	int64_t max_len;           /* longest l_seq among counted (not secondary / supplementary) records, 0 = none */
 	int64_t first_max_ord;     /* shard-local ordinal of the first counted record of that length, -1 = none */
 	int64_t first_paired_ord;  /* shard-local ordinal of the first record that sets paired_end, -1 = none */
@@ -612,7 +612,8 @@ int ngsqc_scan_mapping_partial(ngsqc_handle* h, const ngsqc_mapping_params* p, n
  * additive over shards). Every BGZF member of the shard is inflated once for all consumers; the shard's first records are kept in the form the
  * cross-shard fix-ups need, so ngsqc_scan_mapping_finish does not inflate anything again. read_qc is not available on shards. */
 int ngsqc_run_job_partial(ngsqc_handle* h, const ngsqc_job_desc* job, ngsqc_job_result* result, ngsqc_shard_summary* out);
-/* coverage tools on a shard: ngsqc_scan_depth without the final prefix sum (the depth scan has no order-dependent carries) */
+/* coverage tools on a shard: ngsqc_scan_depth without the final prefix sum (the depth scan has no order-dependent carries). No summary is exchanged: the
+ * shards' chains are checked where their arrays meet, in ngsqc_depth_reduce */
 int ngsqc_scan_depth_partial(ngsqc_handle* h, const ngsqc_depth_params* p);
 /* returns NGSQC_E_FORMAT (message via ngsqc_last_error(NULL)) when the shards' record chains do not join */
 int ngsqc_plan_shard_fix(const ngsqc_shard_summary* all, int n_shards, int shard, ngsqc_shard_fix* out);
@@ -622,7 +623,9 @@ int ngsqc_depth_device(ngsqc_handle* h, void** dev_ptr, int64_t* n_slots);
 int ngsqc_depth_diff_copy(ngsqc_handle* h, int32_t* out, int64_t cap);       /* host copy of the same array (CPU collectives) */
 int ngsqc_depth_diff_set(ngsqc_handle* h, const int32_t* in, int64_t n);
 /* dst's difference array += the arrays of the other shard handles; arrays on other GPUs are pulled with peer copies over xGMI
- * (no host staging). All handles must have scanned the same regions with ngsqc_scan_*_partial. */
+ * (no host staging). All handles must have scanned the same regions with ngsqc_scan_*_partial. The shard handles among dst and srcs are held to the
+ * chain rule of ngsqc_plan_shard_fix, in the order of their shard index: NGSQC_E_FORMAT (same message, on dst) when their record chains do not join,
+ * and nothing is added. */
 int ngsqc_depth_reduce(ngsqc_handle* dst, ngsqc_handle* const* srcs, int n_srcs);
 int ngsqc_depth_finalize(ngsqc_handle* h);                                    /* difference array -> per-base depth (K6 prefix sum) */
 

@@ -556,9 +556,10 @@ def _windows_array(windows):
 class Handle:
     """One open BAM on one GPU (ngsqc_handle)."""
 
-    def __init__(self, path=None, data=None, device=0, shard=None, voff_range=None, regions=None):
+    def __init__(self, path=None, data=None, device=0, shard=None, voff_range=None, regions=None, head_members=None):
         """shard=(i, n): own the records that start inside the i-th of n contiguous BGZF-member ranges of the BAM.
-        voff_range=(beg, end): the records of a virtual-offset range of the file at `path` (from bai_range: index-driven partial decode)."""
+        voff_range=(beg, end): the records of a virtual-offset range of the file at `path` (from bai_range: index-driven partial decode).
+        head_members=k: the records that start in the first k BGZF members from the one that holds the first record (ngsqc_open_head)."""
         L = lib()
         h = C.c_void_p()
         si, sn = (int(shard[0]), int(shard[1])) if shard is not None else (0, 1)
@@ -569,6 +570,9 @@ class Handle:
             arr = (NR * max(len(regions), 1))(*[NR(os.fsencode(c), int(a), int(b)) for c, a, b in regions])
             L.ngsqc_open_regions.restype = C.c_int; L.ngsqc_open_regions.argtypes = [C.c_char_p, C.c_int, C.c_void_p, C.c_int64, C.POINTER(C.c_void_p)]
             rc = L.ngsqc_open_regions(os.fsencode(path), device, C.cast(arr, C.c_void_p), len(regions), C.byref(h))
+        elif head_members is not None:
+            L.ngsqc_open_head.restype = C.c_int; L.ngsqc_open_head.argtypes = [C.c_char_p, C.c_int, C.c_int64, C.POINTER(C.c_void_p)]
+            rc = L.ngsqc_open_head(os.fsencode(path), device, int(head_members), C.byref(h))
         elif voff_range is not None:
             L.ngsqc_open_range.restype = C.c_int; L.ngsqc_open_range.argtypes = [C.c_char_p, C.c_int, C.c_uint64, C.c_uint64, C.POINTER(C.c_void_p)]
             rc = L.ngsqc_open_range(os.fsencode(path), device, int(voff_range[0]), int(voff_range[1]), C.byref(h))

@@ -215,6 +215,7 @@ struct ngsqc_handle
 	int64_t shard_limit = -1;              // rebased inflated offset of the first byte that is NOT owned
 	int64_t shard_u_base = 0;              // inflated offset (whole file) of the handle's first member
 	int64_t shard_first_abs = -1, shard_exit_abs = -1; int shard_last_tile = -1;
+	bool shard_anchored = true;            // the running tile stream knows where its record chain starts (a shard behind the header: from the first tile whose guess anchors it)
 	bool verify_crc = osw.verify_crc;   // (false for the image made of a CRAM whose qualities the device decodes, whatever the switch says)
 	// H2D of the compressed image in the background (ngsqc_open of a path): host threads copy pieces in file order, every piece has an event that
 	// the K1 chunk stream waits for; the mapping of the file lives until the last piece is on the device

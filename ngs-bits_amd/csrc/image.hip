@@ -698,11 +698,12 @@ void open_range_common(ngsqc_handle* h, const uint8_t* bytes, size_t n, int devi
 	{
 		if (co_beg >= n || co_end > n) throw ArgError("virtual offset behind the end of the file");
 		size_t o2 = co_beg; uint64_t u2 = 0;
+		if (!bgzf_member_at(bytes, n, co_beg)) throw ArgError("virtual offset does not name a BGZF block of this file");   // (before the walk, which would call the file damaged)
 		// members from the one that holds `beg` up to the one that holds `end` (inclusive when `end` lies inside it)
 		walk_bgzf(bytes, n, o2, (end & 0xffff) ? co_end + 1 : co_end, INT64_MAX, u2, h->blocks, h->crc, &foff);
 		// A virtual offset may name an EMPTY member (bgzf_tell of a record that starts right behind a member end gives offset 0 of whatever member follows):
 		// the walk drops empty members from the table, so the start is checked against the file, not against the first table entry
-		if (!bgzf_member_at(bytes, n, co_beg) || (!h->blocks.empty() && foff[0] != co_beg && (beg & 0xffff))) throw ArgError("virtual offset does not name a BGZF block of this file");
+		if (!h->blocks.empty() && foff[0] != co_beg && (beg & 0xffff)) throw ArgError("virtual offset does not name a BGZF block of this file");
 	}
 	if (found && end > beg && !h->blocks.empty())   // (a range of empty members only: nothing to read)
 	{

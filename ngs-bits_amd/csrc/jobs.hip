@@ -545,6 +545,28 @@ struct ngsqc_handle::Partial
 };
 
 namespace ngsqc { namespace lib {
+// The ends of the record chain of the handle's last tile stream, as a shard summary reports them: the first record owned and the first record behind the shard -
+// (-1, -1) for a handle that owns no record, whatever its guess found in the members behind its own ones (include/ngsqc.h, ngsqc_shard_summary)
+static void shard_chain_ends(const ngsqc_handle* h, int64_t& first_abs, int64_t& exit_abs)
+{
+	first_abs = h->shard_own_members >= 0 ? h->shard_first_abs : h->first_rec;
+	exit_abs = h->shard_own_members >= 0 ? h->shard_exit_abs : h->total;
+	if (h->tm.n_records == 0 || first_abs < 0) first_abs = exit_abs = -1;
+}
+// The chain rule across shards in file order: a shard's first record is where the chain of the shards in front of it ended (shards that own no record are
+// passed over). -> "" or what does not join. A shard's first record is a guess that only this comparison verifies.
+struct ShardEnds { int shard; int64_t first_abs, exit_abs; };
+static std::string shard_chain_break(const std::vector<ShardEnds>& v)
+{
+	int64_t cur = -1;
+	for (const ShardEnds& e : v)
+	{
+		if (e.first_abs < 0) continue;
+		if (cur >= 0 && e.first_abs != cur) return "shard " + std::to_string(e.shard) + " starts at inflated offset " + std::to_string(e.first_abs) + " but the previous shard's record chain ends at " + std::to_string(cur);
+		cur = e.exit_abs;
+	}
+	return "";
+}
 void mapping_setup(ngsqc_handle* h, const ngsqc_mapping_params* p, ngsqc_handle::Partial& st)
 {
 	if (!p) throw ArgError("null argument");
@@ -716,8 +738,7 @@ void run_job(ngsqc_handle* h, const ngsqc_job_desc* j, ngsqc_job_result* r, ngsq
 		{
 			const unsigned long long key = map.scan.best_key;
 			shard_out->n_records = h->tm.n_records;
-			shard_out->first_abs = h->shard_own_members >= 0 ? h->shard_first_abs : (h->tm.n_records ? h->first_rec : -1);
-			shard_out->exit_abs = h->shard_own_members >= 0 ? h->shard_exit_abs : (h->tm.n_records ? h->total : -1);
+			shard_chain_ends(h, shard_out->first_abs, shard_out->exit_abs);
 			shard_out->max_len = (int64_t)(key >> 40);
 			shard_out->first_max_ord = key ? (int64_t)(0xFFFFFFFFFFull - (key & 0xFFFFFFFFFFull)) : -1;
 			shard_out->first_paired_ord = map.scan.first_paired != ~0ull ? (int64_t)map.scan.first_paired : -1;
@@ -866,6 +887,16 @@ int ngsqc_depth_reduce(ngsqc_handle* dst, ngsqc_handle* const* srcs, int n_srcs)
 		if (n_srcs < 0 || (n_srcs && !srcs)) throw ArgError("null argument");
 		DepthSet& D = cur_depth(dst);
 		if (D.depth_ready) throw ArgError("the depth array is already finalized (prefix-summed)");
+		// The depth scan of a shard exchanges no summary (ngsqc_scan_depth_partial): this is where its shards meet, so the chain rule of ngsqc_plan_shard_fix is
+		// held here, over the shard handles given (dst and srcs, by shard index) - a false guess whose chain rejoins the true one must not add its depth unseen
+		{
+			std::vector<ShardEnds> ends;
+			auto add = [&](const ngsqc_handle* x) { if (x && x->n_shards > 1 && !x->selection && x->shard_own_members >= 0) { ShardEnds e{x->shard, -1, -1}; shard_chain_ends(x, e.first_abs, e.exit_abs); ends.push_back(e); } };
+			add(dst); for (int i = 0; i < n_srcs; ++i) if (srcs[i] != dst) add(srcs[i]);
+			std::stable_sort(ends.begin(), ends.end(), [](const ShardEnds& a, const ShardEnds& b) { return a.shard < b.shard; });
+			const std::string bad = shard_chain_break(ends);
+			if (!bad.empty()) throw FormatError(bad);
+		}
 		DevBuf<int32_t> stage;
 		for (int i = 0; i < n_srcs; ++i)
 		{
@@ -903,13 +934,10 @@ int ngsqc_depth_finalize(ngsqc_handle* h)
 int ngsqc_plan_shard_fix(const ngsqc_shard_summary* all, int n_shards, int shard, ngsqc_shard_fix* out)
 {
 	if (!all || !out || n_shards < 1 || shard < 0 || shard >= n_shards) return NGSQC_E_ARG;
-	int64_t cur = -1;
-	for (int s = 0; s < n_shards; ++s)
-	{
-		if (all[s].first_abs < 0) continue;
-		if (cur >= 0 && all[s].first_abs != cur) { g_open_error = "shard " + std::to_string(s) + " starts at inflated offset " + std::to_string(all[s].first_abs) + " but the previous shard's record chain ends at " + std::to_string(cur); return NGSQC_E_FORMAT; }
-		cur = all[s].exit_abs;
-	}
+	std::vector<ShardEnds> ends;
+	for (int s = 0; s < n_shards; ++s) ends.push_back(ShardEnds{s, all[s].first_abs, all[s].exit_abs});
+	const std::string bad = shard_chain_break(ends);
+	if (!bad.empty()) { g_open_error = bad; return NGSQC_E_FORMAT; }
 	int64_t gmax = 0; int s_max = -1, s_paired = -1;
 	for (int s = 0; s < n_shards; ++s) if (all[s].max_len > gmax) { gmax = all[s].max_len; }
 	for (int s = 0; s < n_shards; ++s) if (s_max < 0 && gmax > 0 && all[s].max_len == gmax) s_max = s;

@@ -143,7 +143,7 @@ void index_tile(ngsqc_handle* h, int t)
 	const int nt = (int)h->tiles.size();
 	const bool last = t == nt - 1;
 	const int64_t first = h->tiles[(size_t)t].first, nm = h->tiles[(size_t)t].second;
-	if (t == 0) { h->carry_len = 0; h->next_ord_base = 0; h->expected_abs = h->first_rec; }
+	if (t == 0) { h->carry_len = 0; h->next_ord_base = 0; h->expected_abs = h->first_rec; h->shard_anchored = h->first_rec >= 0; h->shard_first_abs = -1; }
 	const int64_t u_lo = (int64_t)h->blocks[(size_t)first].upos;
 	const int64_t u_hi = (int64_t)h->blocks[(size_t)(first + nm - 1)].upos + h->blocks[(size_t)(first + nm - 1)].usize;
 	const int64_t prefix = h->carry_len;
@@ -152,7 +152,10 @@ void index_tile(ngsqc_handle* h, int t)
 	const BlockDesc* d_desc = h->d_kdesc.p + first;
 	// entries: entry 0 = the carried prefix, then the members - on the fast path each cut into 2^ksh pieces with a walker of its own (common.h entry_range;
 	// NGSQC_WALKERS = 1 / 2 / 4 / 8, default 1: a tile of the 30x file was 190 k members = three waves per SIMD in round 5 and is 655 k since round 6 - more waves than the chip holds buy nothing, profiles/r05_scan_probe.txt); the general path below (and a shard's first tile, whose chain is anchored by a guess) works on whole members
-	const bool anchor_by_guess = t == 0 && h->first_rec < 0;
+	// a shard behind the file header guesses until a tile anchors its chain: a tile that lies inside one record holds no record start, and nothing says that the
+	// next tile begins with one. Such a tile is carried into the next one whole (below): the guess only accepts a record that ends inside the bytes it sees, so
+	// a record start in front of the tile's end - its header cut, or its body - can only be found with the next tile's bytes behind it
+	const bool anchor_by_guess = !h->shard_anchored;
 	int64_t exp0 = prefix ? 0 : (h->expected_abs - u_lo);   // local offset of the first record start of this tile
 	// long reads (round 5): the file's first record says what kind of file this is - a record of more than 8 KiB means members that mostly lie inside one record.
 	// Then nothing is assumed about member starts, and an entry of the fast path is a group of 16 members (common.h entry_range)
@@ -182,7 +185,7 @@ void index_tile(ngsqc_handle* h, int t)
 	auto e_sz = [&](int64_t e) -> int64_t { return e == 0 ? prefix : (int64_t)h->blocks[(size_t)(first + e - 1)].usize; };
 	EvLog& ev = *h->evlog; size_t iv = ev.begin(h->stream, &h->tm.index_ms);   // (the riding scan's kernel is booked as scan time: the interval is cut around it)
 	// a shard behind the file header does not know where its first record starts: every member is guessed and the first
-	// plausible start anchors the chain (checked against the previous shard's chain exit by ngsqc_plan_shard_fix)
+	// plausible start anchors the chain (checked against the previous shard's chain exit by ngsqc_plan_shard_fix, and by ngsqc_depth_reduce for the depth scan)
 	// (with slack: a later tile has one entry more - its carried prefix - and regrowing means hipFree, which waits for all queued K1 work)
 	const size_t ne_max = (size_t)std::max(ne, ne0);   // (the general path below works on whole members whatever the fast path's entries were)
 	h->d_start.ensure_slack(ne_max); h->d_cnt.ensure_slack(ne_max + 1); h->d_next.ensure_slack(ne_max + 1); h->d_base.ensure_slack(ne_max + 1); h->d_bad.ensure(4);   // d_bad: {corrupt records, chain violations} + the offset of a record cut by the tile end (int64, -1: none)
@@ -317,7 +320,9 @@ void index_tile(ngsqc_handle* h, int t)
 	ev.end(iv, h->stream);
 	if (!h->lazy_recoff || h->fused_tile != t || h->shard_own_members >= 0) ensure_recoff(h);
 	iv = ev.begin(h->stream, &h->tm.index_ms);
-	if (t == 0 && h->shard_own_members >= 0) h->shard_first_abs = (found_start && (n_rec > 0 || straddle >= 0)) ? h->shard_u_base + u_lo + (exp0 - prefix) : -1;
+	if (anchor_by_guess && found_start) h->shard_anchored = true;
+	// the first record of the handle's chain: in the first tile that holds a record start (a shard's first tiles may hold header bytes alone, or lie inside one record)
+	if (h->shard_own_members >= 0 && h->shard_first_abs < 0 && found_start && (n_rec > 0 || straddle >= 0)) h->shard_first_abs = h->shard_u_base + u_lo + (exp0 - prefix);
 	if (h->shard_own_members >= 0)
 	{
 		// records that start at or behind the shard limit belong to the next shard (recoff is ascending)
@@ -346,6 +351,7 @@ void index_tile(ngsqc_handle* h, int t)
 		}
 	}
 	ev.end(iv, h->stream);
+	if (anchor_by_guess && !found_start && !last) straddle = 0;   // no anchor yet: everything seen so far goes in front of the next tile (entry 0 there), as one straddling record would
 	// ---- publish tile state ----
 	h->cur_tile = t; h->tile_prefix = prefix; h->tile_total = total; h->tile_u_lo = u_lo; h->tile_ord_base = h->next_ord_base;
 	h->n_rec = n_rec; h->tm.n_records += n_rec;
