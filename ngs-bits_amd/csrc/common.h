@@ -1,6 +1,7 @@
 // Shared declarations of the HIP hot path (libngsqc_hip.so). gfx950 only — no CUDA paths, no compat shims.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <cstddef>
 #include <cstdint>
 #include <cstdio>
 #include <stdexcept>
@@ -12,6 +13,7 @@
 #include "k1_types.h"
 #include "cram_plan.h"
 #include "switches.h"
+#include "postable.h"
 
 namespace ngsqc {
 
@@ -137,12 +139,16 @@ struct ScanParams
 	// the scan fused into K2's chain walk (launch_walk_scan): records are named (entry << NAME_SHIFT | k) until the counts are scanned (entry_base != null: the
 	// long list holds such names); sgn = -1 takes a tile's contributions back (a tile that turned out not to be laid out like an htslib file)
 	// the site pileup of the job riding the same walk: records whose span holds a known site leave their offset in list (list == nullptr: no pileup rides)
-	struct Pile { const int32_t* site_pos = nullptr; const int32_t* tid_first = nullptr; const int32_t* tid_last = nullptr; const int32_t* bucket = nullptr; const int64_t* tid_bucket0 = nullptr;
+	struct Pile { PosTable sites{};   // (postable.h)
 	              int64_t* list = nullptr; unsigned long long* count = nullptr; int64_t cap = 0; int32_t min_mapq = 0, include_npp = 0; } pile;
 	// MODE_DEPTH with min_baseq riding the walk (round 5): a record that overlaps a region leaves its offset here, a wave per record masks its low-quality bases afterwards
 	int64_t* bq_list = nullptr; unsigned long long* bq_count = nullptr; int64_t bq_cap = 0;
 	const int64_t* entry_base = nullptr; int32_t sgn = 1; int32_t tile_slots = 0; int64_t scan_limit = INT64_MAX;   // scan_limit: (a shard) records that start at or behind this tile-local offset are walked, not scanned
 };
+// walk_scan_kernel takes ScanParams by value: the layout its kernel arguments have had since the table's five pointers were loose members of Pile
+static_assert(sizeof(PosTable) == 40 && sizeof(ScanParams::Pile) == 72 && offsetof(ScanParams::Pile, list) == 40 && offsetof(ScanParams::Pile, include_npp) == 68, "ScanParams::Pile moved");
+static_assert(sizeof(ScanParams) == 368 && offsetof(ScanParams, pile) == 248 && offsetof(ScanParams, bq_list) == 320 && offsetof(ScanParams, entry_base) == 344 &&
+              offsetof(ScanParams, sgn) == 352 && offsetof(ScanParams, scan_limit) == 360, "ScanParams moved");
 
 void launch_scan(const ScanParams& p, hipStream_t s);
 // K2's chain walk (what launch_index_count does) with the scan of every record the walk passes: one read of a record's first line instead of two
@@ -157,20 +163,17 @@ size_t prefix_fix_scratch_words(int64_t upto);
 void launch_prefix_capture(const ScanParams& p, int64_t n, uint32_t* d_head, hipStream_t s);
 
 // site pileup (BamReader::getPileup SNP counts for a table of sites; counts = u32[n_sites][8])
-constexpr int PILEUP_BUCKET_SHIFT = 16;   // 64 kb position buckets per reference: bucket -> first site at or behind the bucket start
-void launch_pileup(const uint8_t* infl, const int64_t* recoff, int64_t n_rec, int n_ref, const int32_t* site_pos, const int32_t* tid_first, const int32_t* tid_last,
-                   const int32_t* bucket, const int64_t* tid_bucket0, int min_mapq, int min_baseq, int include_npp, uint32_t* counts,
+void launch_pileup(const uint8_t* infl, const int64_t* recoff, int64_t n_rec, int n_ref, const PosTable& sites, int min_mapq, int min_baseq, int include_npp, uint32_t* counts,
                    int64_t* long_list, unsigned long long* long_count, hipStream_t s);
-void launch_pileup_long(const uint8_t* infl, const int64_t* recoff, const int64_t* long_list, const unsigned long long* d_n_long /* count on the device */, int64_t n_long_max, const int32_t* site_pos, const int32_t* tid_last,
-                        const int32_t* bucket, const int64_t* tid_bucket0, int min_baseq, uint32_t* counts, hipStream_t s);
+void launch_pileup_long(const uint8_t* infl, const int64_t* recoff, const int64_t* long_list, const unsigned long long* d_n_long /* count on the device */, int64_t n_long_max, const PosTable& sites,
+                        int min_baseq, uint32_t* counts, hipStream_t s);
 
-// indel windows (indel.hip: BamReader::getIndels for a table of windows; counts = u32[n_windows][8], see there). start: 1-based window starts, sorted per
-// reference; win: the rest of each window; pool: query alleles and reference slices; buckets as in the site pileup; tid_maxlen: longest window of a reference
+// indel windows (indel.hip: BamReader::getIndels for a table of windows; counts = u32[n_windows][8], see there). tab: the 1-based window starts (postable.h);
+// win: the rest of each window; pool: query alleles and reference slices; tid_maxlen: longest window of a reference
 struct IndelWin { int32_t end, kind, len, ref_len; int64_t qoff, soff; };   // ref_len: length of the window's reference (where FastaFileIndex::seq cuts a deletion)
 struct IndelTables
 {
-	const int32_t* start; const IndelWin* win; const uint8_t* pool;
-	const int32_t* tid_first; const int32_t* tid_last; const int32_t* tid_maxlen; const int32_t* bucket; const int64_t* tid_bucket0;
+	PosTable tab; const IndelWin* win; const uint8_t* pool; const int32_t* tid_maxlen;
 	int32_t n_ref, include_npp;
 };
 void launch_indel(const uint8_t* infl, const int64_t* recoff, int64_t n_rec, const IndelTables& w, uint32_t* counts, int64_t* long_list, unsigned long long* long_count, hipStream_t s);

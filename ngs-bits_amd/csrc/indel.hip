@@ -20,12 +20,7 @@ namespace ngsqc {
 // first window of reference tid [first, last) whose start is >= x
 __device__ __forceinline__ int win_lower(const IndelTables& w, int tid, int first, int last, long long x)
 {
-	if (x <= 1) return first;
-	const int64_t b0 = w.tid_bucket0[tid], nbk = w.tid_bucket0[tid + 1] - b0;
-	int64_t bi = x >> PILEUP_BUCKET_SHIFT; if (bi >= nbk) bi = nbk - 1;
-	int lo = w.bucket[b0 + bi], hi = bi + 1 < nbk ? w.bucket[b0 + bi + 1] : last;
-	while (lo < hi) { const int m = (lo + hi) >> 1; if (w.start[m] < x) lo = m + 1; else hi = m; }
-	return lo;
+	return postable_lower_bsearch(w.tab, tid, first, last, x);
 }
 
 __device__ __forceinline__ char seq_char(const RecView& r, int i)
@@ -57,7 +52,7 @@ __device__ __forceinline__ void indel_event(const IndelTables& w, const RecView&
 		const int have = (int)max(0ll, min((long long)len, left));
 		if (have == q.len)
 		{
-			const int64_t s = q.soff + (gp - w.start[i]);
+			const int64_t s = q.soff + (gp - w.tab.pos[i]);
 			match = true;
 			for (int j = 0; j < have && match; ++j) match = w.pool[s + j] == w.pool[q.qoff + j];
 		}
@@ -80,7 +75,7 @@ __global__ __launch_bounds__(256) void indel_kernel(const uint8_t* __restrict__ 
 		RecView r = load_rec(infl, recoff[li]);
 		if (read_filtered(r, w.include_npp)) continue;
 		if (r.tid < 0 || r.tid >= w.n_ref) continue;
-		const int first = w.tid_first[r.tid], last = w.tid_last[r.tid];
+		const int first = w.tab.tid_first[r.tid], last = w.tab.tid_last[r.tid];
 		if (first >= last) continue;
 		rec_apply_cg(r);
 		if (r.n_cigar > (uint32_t)LONG_CIGAR) { long_list[atomicAdd(long_count, 1ull)] = li; continue; }   // wave-per-record path (indel_long_kernel)
@@ -96,12 +91,12 @@ __global__ __launch_bounds__(256) void indel_kernel(const uint8_t* __restrict__ 
 		const int a = win_lower(w, r.tid, first, last, start1 - w.tid_maxlen[r.tid] + 1);
 		const bool mq0 = r.mapq == 0;
 		bool any_span = false;
-		for (int i = a; i < last && w.start[i] <= end1; ++i)
+		for (int i = a; i < last && w.tab.pos[i] <= end1; ++i)
 		{
 			if (w.win[i].end < start1) continue;
 			atomicAdd(&counts[8ull * i], 1u);
 			if (mq0) { atomicAdd(&counts[8ull * i + 1], 1u); continue; }
-			if (start1 <= w.start[i] && end1 >= w.win[i].end) { atomicAdd(&counts[8ull * i + 2], 1u); any_span = true; }
+			if (start1 <= w.tab.pos[i] && end1 >= w.win[i].end) { atomicAdd(&counts[8ull * i + 2], 1u); any_span = true; }
 		}
 		if (!any_span || !idn) continue;
 		long long gp = start1; int rp = 0;
@@ -110,9 +105,9 @@ __global__ __launch_bounds__(256) void indel_kernel(const uint8_t* __restrict__ 
 			const uint32_t c = ld32(r.cigar + 4ull * k), op = c & 15u; const int len = (int)(c >> 4);
 			if (op == 1u || op == 2u || op == 3u)
 			{
-				for (int i = a; i < last && w.start[i] <= end1; ++i)
+				for (int i = a; i < last && w.tab.pos[i] <= end1; ++i)
 				{
-					const int ws = w.start[i], we = w.win[i].end;
+					const int ws = w.tab.pos[i], we = w.win[i].end;
 					if (start1 > ws || end1 < we) continue;   // (spanning records only)
 					if (op == 3u) { if (gp <= ws && gp + len >= we) atomicAdd(&counts[8ull * i + 2], 0xFFFFFFFFu); }
 					else if (gp >= ws && gp <= we) indel_event(w, r, i, op, len, gp, rp, counts);
@@ -122,8 +117,8 @@ __global__ __launch_bounds__(256) void indel_kernel(const uint8_t* __restrict__ 
 			if (op == 0u || op == 1u || op == 4u || op == 7u || op == 8u) rp += len;
 		}
 		if (unknown)
-			for (int i = a; i < last && w.start[i] <= end1; ++i)
-				if (start1 <= w.start[i] && end1 >= w.win[i].end) atomicAdd(&counts[8ull * i + 6], 1u);
+			for (int i = a; i < last && w.tab.pos[i] <= end1; ++i)
+				if (start1 <= w.tab.pos[i] && end1 >= w.win[i].end) atomicAdd(&counts[8ull * i + 6], 1u);
 	}
 }
 
@@ -150,16 +145,16 @@ __global__ __launch_bounds__(256) void indel_long_kernel(const uint8_t* __restri
 		ref_len = wave_sum(ref_len); idn = __any(idn); unknown = __any(unknown);
 		if (ref_len == 0) ref_len = 1;
 		const long long start1 = (long long)r.pos + 1, end1 = (long long)r.pos + ref_len;
-		const int first = w.tid_first[r.tid], last = w.tid_last[r.tid];
+		const int first = w.tab.tid_first[r.tid], last = w.tab.tid_last[r.tid];
 		const int a = win_lower(w, r.tid, first, last, start1 - w.tid_maxlen[r.tid] + 1);
 		const bool mq0 = r.mapq == 0;
 		bool any_span = false;
-		for (int i = a + lane; i < last && w.start[i] <= end1; i += 64)
+		for (int i = a + lane; i < last && w.tab.pos[i] <= end1; i += 64)
 		{
 			if (w.win[i].end < start1) continue;
 			atomicAdd(&counts[8ull * i], 1u);
 			if (mq0) { atomicAdd(&counts[8ull * i + 1], 1u); continue; }
-			if (start1 <= w.start[i] && end1 >= w.win[i].end)
+			if (start1 <= w.tab.pos[i] && end1 >= w.win[i].end)
 			{
 				atomicAdd(&counts[8ull * i + 2], 1u); any_span = true;
 				if (unknown && idn) atomicAdd(&counts[8ull * i + 6], 1u);
@@ -179,17 +174,17 @@ __global__ __launch_bounds__(256) void indel_long_kernel(const uint8_t* __restri
 			const long long gp = g_base + g - g_own, rpos = rp_base + rp - rp_own;   // positions IN FRONT OF this lane's operation
 			if (k < r.n_cigar && (op == 1u || op == 2u))
 			{
-				for (int i = win_lower(w, r.tid, first, last, gp - w.tid_maxlen[r.tid] + 1); i < last && w.start[i] <= gp; ++i)
+				for (int i = win_lower(w, r.tid, first, last, gp - w.tid_maxlen[r.tid] + 1); i < last && w.tab.pos[i] <= gp; ++i)
 				{
-					const int ws = w.start[i], we = w.win[i].end;
+					const int ws = w.tab.pos[i], we = w.win[i].end;
 					if (start1 <= ws && end1 >= we && gp <= we) indel_event(w, r, i, op, len, gp, (int)rpos, counts);
 				}
 			}
 			else if (k < r.n_cigar && op == 3u)
 			{
-				for (int i = win_lower(w, r.tid, first, last, gp); i < last && w.start[i] <= gp + len; ++i)
+				for (int i = win_lower(w, r.tid, first, last, gp); i < last && w.tab.pos[i] <= gp + len; ++i)
 				{
-					const int ws = w.start[i], we = w.win[i].end;
+					const int ws = w.tab.pos[i], we = w.win[i].end;
 					if (start1 <= ws && end1 >= we && gp + len >= we) atomicAdd(&counts[8ull * i + 2], 0xFFFFFFFFu);
 				}
 			}

@@ -10,20 +10,16 @@ void setup_regions(ngsqc_handle* h, DepthSet& D, const ngsqc_region* regions, in
 	const int n_ref = (int)h->ref_names.size();
 	D.regions.assign(regions, regions + (n > 0 ? n : 0));
 	D.doff.assign((size_t)n + 1, 0); D.rlen.assign((size_t)n, 0);
-	std::vector<int32_t> rs((size_t)n), re((size_t)n), tf((size_t)std::max(n_ref, 1), 0), tl((size_t)std::max(n_ref, 1), 0);
-	std::vector<uint8_t> seen((size_t)std::max(n_ref, 1), 0);
+	std::vector<int32_t> rs((size_t)n), re((size_t)n), tf, tl;
 	int64_t slots = 0, bases = 0;
-	for (int64_t i = 0; i < n; ++i)
-	{
-		const ngsqc_region& r = regions[i];
-		if (r.tid < 0 || r.tid >= n_ref) throw ArgError("region with invalid reference id");
-		if (r.start < 1 || r.end < r.start) throw ArgError("invalid region range");
-		if (i > 0 && regions[i - 1].tid == r.tid) { if (regions[i - 1].end >= r.start) throw ArgError("Merged and sorted BED file required for coverage details statistics!"); }
-		else { if (seen[r.tid]) throw ArgError("Merged and sorted BED file required for coverage details statistics!"); seen[r.tid] = 1; tf[r.tid] = (int32_t)i; }
-		tl[r.tid] = (int32_t)i + 1;
-		rs[i] = r.start; re[i] = r.end; D.rlen[i] = r.end - r.start + 1; D.doff[i] = slots;
-		slots += (int64_t)D.rlen[i] + 1; bases += D.rlen[i];
-	}
+	const char* const merged = "Merged and sorted BED file required for coverage details statistics!";
+	postable_runs<ArgError>(regions, n, n_ref, {"region with invalid reference id", merged, merged}, tf, tl,
+		[&](int64_t i, const ngsqc_region& r) {
+			if (r.start < 1 || r.end < r.start) throw ArgError("invalid region range");
+			rs[i] = r.start; re[i] = r.end; D.rlen[i] = r.end - r.start + 1; D.doff[i] = slots;
+			slots += (int64_t)D.rlen[i] + 1; bases += D.rlen[i];
+		},
+		[](const ngsqc_region& prev, const ngsqc_region& r) { return prev.end < r.start; });
 	D.doff[n] = slots; D.n_slots = slots; D.roi_bases = bases;
 	D.d_reg_start.upload(rs, h->stream); D.d_reg_end.upload(re, h->stream); D.d_reg_len.upload(D.rlen, h->stream);
 	D.d_tid_first.upload(tf, h->stream); D.d_tid_last.upload(tl, h->stream);
@@ -249,10 +245,22 @@ void bind_regions(ScanParams& sp, DepthSet& D)
 	sp.diff = D.d_depth.p;
 }
 
+// a position table on the device (postable.h): its owner collects positions and runs, the buckets are made on the way up
+struct PosTableDev
+{
+	DevBuf<int32_t> pos, tid_first, tid_last, bucket; DevBuf<int64_t> tid_bucket0;
+	void upload(ngsqc_handle* h, PosTableHost& t)   // (t must outlive the copies: the caller waits for the stream)
+	{
+		postable_buckets(t, h->ref_lens.data(), (int)h->ref_names.size());
+		pos.upload(t.pos, h->stream); tid_first.upload(t.tid_first, h->stream); tid_last.upload(t.tid_last, h->stream); bucket.upload(t.bucket, h->stream); tid_bucket0.upload(t.tid_bucket0, h->stream);
+	}
+	PosTable view() const { return PosTable{pos.p, tid_first.p, tid_last.p, bucket.p, tid_bucket0.p}; }
+};
+
 // site pileup of a table of known sites (BamReader::getPileup per site in the reference)
 struct PileupState
 {
-	DevBuf<int32_t> d_pos, d_tf, d_tl, d_bucket; DevBuf<int64_t> d_tb0; DevBuf<uint32_t> d_cnt; DevBuf<unsigned long long> d_nlong;
+	PosTableDev tab; DevBuf<uint32_t> d_cnt; DevBuf<unsigned long long> d_nlong;
 	int64_t n_sites = 0; int n_ref = 0; int min_mapq = 0, min_baseq = 0, include_npp = 0; double stage_ms = 0;
 	// Round 4: when the job's mapping scan rides K2's chain walk, the walk also names the records whose reference span holds a site (scan.hip pile_candidate):
 	// the pileup of such a tile runs over that list - 0.15 % of the records of a 30x WGS - instead of reading every record again (24 -> 2 ms per step of the 30x file)
@@ -262,7 +270,7 @@ struct PileupState
 	{
 		if (n_sites == 0) return;
 		d_cand.ensure((size_t)CAND_CAP); d_ncand.ensure(1);
-		sp.pile.site_pos = d_pos.p; sp.pile.tid_first = d_tf.p; sp.pile.tid_last = d_tl.p; sp.pile.bucket = d_bucket.p; sp.pile.tid_bucket0 = d_tb0.p;
+		sp.pile.sites = tab.view();
 		sp.pile.list = d_cand.p; sp.pile.count = d_ncand.p; sp.pile.cap = CAND_CAP; sp.pile.min_mapq = min_mapq; sp.pile.include_npp = include_npp;
 		rider = scan;
 	}
@@ -270,30 +278,14 @@ struct PileupState
 	{
 		n_sites = n; min_mapq = mq; min_baseq = bq; include_npp = npp ? 1 : 0; stage_ms = 0;
 		n_ref = (int)h->ref_names.size();
-		std::vector<int32_t> pos((size_t)n_sites), tf((size_t)std::max(n_ref, 1), 0), tl((size_t)std::max(n_ref, 1), 0);
-		std::vector<uint8_t> seen((size_t)std::max(n_ref, 1), 0);
-		for (int64_t i = 0; i < n_sites; ++i)
-		{
-			const ngsqc_region& r = sites[i];
-			if (r.tid < 0 || r.tid >= n_ref) throw ArgError("site with invalid reference id");
-			if (r.start < 1 || r.end != r.start) throw ArgError("a site is a single 1-based position (start == end)");
-			if (i > 0 && sites[i - 1].tid == r.tid) { if (sites[i - 1].start > r.start) throw ArgError("sites must be sorted by position within a reference"); }
-			else { if (seen[(size_t)r.tid]) throw ArgError("sites of one reference must be contiguous"); seen[(size_t)r.tid] = 1; tf[(size_t)r.tid] = (int32_t)i; }
-			tl[(size_t)r.tid] = (int32_t)i + 1; pos[(size_t)i] = r.start;
-		}
-		// 64 kb position buckets per reference (only references that have sites get buckets)
-		std::vector<int64_t> tb0((size_t)n_ref + 1, 0); std::vector<int32_t> bucket;
-		for (int t = 0; t < n_ref; ++t)
-		{
-			tb0[(size_t)t] = (int64_t)bucket.size();
-			if (tf[(size_t)t] >= tl[(size_t)t]) continue;
-			const int64_t nb = (std::max<int64_t>(h->ref_lens[(size_t)t], pos[(size_t)tl[(size_t)t] - 1]) >> PILEUP_BUCKET_SHIFT) + 2;
-			int32_t i = tf[(size_t)t];
-			for (int64_t b = 0; b < nb; ++b) { const int64_t lo = b << PILEUP_BUCKET_SHIFT; while (i < tl[(size_t)t] && pos[(size_t)i] < lo) ++i; bucket.push_back(i); }
-		}
-		tb0[(size_t)n_ref] = (int64_t)bucket.size();
-		if (bucket.empty()) bucket.push_back(0);
-		d_pos.upload(pos, h->stream); d_tf.upload(tf, h->stream); d_tl.upload(tl, h->stream); d_bucket.upload(bucket, h->stream); d_tb0.upload(tb0, h->stream);
+		PosTableHost t; t.pos.resize((size_t)n_sites);
+		postable_runs<ArgError>(sites, n_sites, n_ref, {"site with invalid reference id", "sites must be sorted by position within a reference", "sites of one reference must be contiguous"}, t.tid_first, t.tid_last,
+			[&](int64_t i, const ngsqc_region& r) {
+				if (r.start < 1 || r.end != r.start) throw ArgError("a site is a single 1-based position (start == end)");
+				t.pos[(size_t)i] = r.start;
+			},
+			[](const ngsqc_region& prev, const ngsqc_region& r) { return prev.start <= r.start; });
+		tab.upload(h, t);
 		d_cnt.ensure((size_t)n_sites * 8); d_nlong.ensure(1);
 		HIPCHK(hipMemsetAsync(d_cnt.p, 0, (size_t)n_sites * 8 * sizeof(uint32_t), h->stream));
 		HIPCHK(hipStreamSynchronize(h->stream));
@@ -308,9 +300,9 @@ struct PileupState
 		if (!offs) offs = ensure_recoff(h);
 		h->d_long.ensure_slack((size_t)std::max<int64_t>(n, 1));
 		HIPCHK(hipMemsetAsync(d_nlong.p, 0, sizeof(unsigned long long), h->stream));
-		launch_pileup(c.infl, offs, n, n_ref, d_pos.p, d_tf.p, d_tl.p, d_bucket.p, d_tb0.p, min_mapq, min_baseq, include_npp, d_cnt.p, h->d_long.p, d_nlong.p, h->stream);
+		launch_pileup(c.infl, offs, n, n_ref, tab.view(), min_mapq, min_baseq, include_npp, d_cnt.p, h->d_long.p, d_nlong.p, h->stream);
 		// records with long CIGARs: a wave each; how many there are stays on the device (no wait between the two kernels)
-		launch_pileup_long(c.infl, offs, h->d_long.p, d_nlong.p, n, d_pos.p, d_tl.p, d_bucket.p, d_tb0.p, min_baseq, d_cnt.p, h->stream);
+		launch_pileup_long(c.infl, offs, h->d_long.p, d_nlong.p, n, tab.view(), min_baseq, d_cnt.p, h->stream);
 		h->evlog->end(iv, h->stream);
 	}
 	void end(ngsqc_handle* h, int64_t* counts)
@@ -327,48 +319,33 @@ struct PileupState
 // a window sees at most one count per record of the file
 struct IndelState
 {
-	DevBuf<int32_t> d_start, d_tf, d_tl, d_maxlen, d_bucket; DevBuf<int64_t> d_tb0; DevBuf<IndelWin> d_win; DevBuf<uint8_t> d_pool; DevBuf<uint32_t> d_cnt; DevBuf<unsigned long long> d_nlong;
+	PosTableDev tab; DevBuf<int32_t> d_maxlen; DevBuf<IndelWin> d_win; DevBuf<uint8_t> d_pool; DevBuf<uint32_t> d_cnt; DevBuf<unsigned long long> d_nlong;
 	IndelTables t{}; int64_t n = 0; double stage_ms = 0;
 	void begin(ngsqc_handle* h, const ngsqc_indel_window* w, int64_t nw, int32_t npp)
 	{
 		n = nw; stage_ms = 0;
 		const int n_ref = (int)h->ref_names.size();
-		std::vector<int32_t> start((size_t)n), tf((size_t)std::max(n_ref, 1), 0), tl((size_t)std::max(n_ref, 1), 0), maxlen((size_t)std::max(n_ref, 1), 1);
+		PosTableHost pt; pt.pos.resize((size_t)n);   // the window starts
+		std::vector<int32_t> maxlen((size_t)std::max(n_ref, 1), 1);
 		std::vector<IndelWin> win((size_t)n); std::vector<uint8_t> pool;
-		std::vector<uint8_t> seen((size_t)std::max(n_ref, 1), 0);
-		for (int64_t i = 0; i < n; ++i)
-		{
-			const ngsqc_indel_window& x = w[i];
-			if (x.tid < 0 || x.tid >= n_ref) throw ArgError("window with invalid reference id");
-			if (x.start < 1 || x.end < x.start) throw ArgError("invalid window range");
-			if (x.kind < NGSQC_ALLELE_NONE || x.kind > NGSQC_ALLELE_DEL || x.len < 0 || (x.kind != NGSQC_ALLELE_NONE && x.len > 0 && !x.allele)) throw ArgError("invalid window allele");
-			if (x.kind == NGSQC_ALLELE_DEL && x.len > 0 && !x.ref_slice) throw ArgError("a deletion window needs its reference slice");
-			if (i > 0 && w[i - 1].tid == x.tid) { if (w[i - 1].start > x.start) throw ArgError("windows must be sorted by start within a reference"); }
-			else { if (seen[(size_t)x.tid]) throw ArgError("windows of one reference must be contiguous"); seen[(size_t)x.tid] = 1; tf[(size_t)x.tid] = (int32_t)i; }
-			tl[(size_t)x.tid] = (int32_t)i + 1; start[(size_t)i] = x.start;
-			maxlen[(size_t)x.tid] = std::max(maxlen[(size_t)x.tid], x.end - x.start + 1);
-			IndelWin& d = win[(size_t)i]; d.end = x.end; d.kind = x.kind; d.len = x.kind == NGSQC_ALLELE_NONE ? 0 : x.len; d.ref_len = (int32_t)std::min<int64_t>(h->ref_lens[(size_t)x.tid], INT32_MAX); d.qoff = (int64_t)pool.size(); d.soff = d.qoff;
-			if (d.len > 0) pool.insert(pool.end(), (const uint8_t*)x.allele, (const uint8_t*)x.allele + d.len);
-			if (x.kind == NGSQC_ALLELE_DEL && d.len > 0) { d.soff = (int64_t)pool.size(); pool.insert(pool.end(), (const uint8_t*)x.ref_slice, (const uint8_t*)x.ref_slice + (x.end - x.start + d.len)); }
-		}
+		postable_runs<ArgError>(w, n, n_ref, {"window with invalid reference id", "windows must be sorted by start within a reference", "windows of one reference must be contiguous"}, pt.tid_first, pt.tid_last,
+			[&](int64_t i, const ngsqc_indel_window& x) {
+				if (x.start < 1 || x.end < x.start) throw ArgError("invalid window range");
+				if (x.kind < NGSQC_ALLELE_NONE || x.kind > NGSQC_ALLELE_DEL || x.len < 0 || (x.kind != NGSQC_ALLELE_NONE && x.len > 0 && !x.allele)) throw ArgError("invalid window allele");
+				if (x.kind == NGSQC_ALLELE_DEL && x.len > 0 && !x.ref_slice) throw ArgError("a deletion window needs its reference slice");
+				pt.pos[(size_t)i] = x.start;
+				maxlen[(size_t)x.tid] = std::max(maxlen[(size_t)x.tid], x.end - x.start + 1);
+				IndelWin& d = win[(size_t)i]; d.end = x.end; d.kind = x.kind; d.len = x.kind == NGSQC_ALLELE_NONE ? 0 : x.len; d.ref_len = (int32_t)std::min<int64_t>(h->ref_lens[(size_t)x.tid], INT32_MAX); d.qoff = (int64_t)pool.size(); d.soff = d.qoff;
+				if (d.len > 0) pool.insert(pool.end(), (const uint8_t*)x.allele, (const uint8_t*)x.allele + d.len);
+				if (x.kind == NGSQC_ALLELE_DEL && d.len > 0) { d.soff = (int64_t)pool.size(); pool.insert(pool.end(), (const uint8_t*)x.ref_slice, (const uint8_t*)x.ref_slice + (x.end - x.start + d.len)); }
+			},
+			[](const ngsqc_indel_window& prev, const ngsqc_indel_window& x) { return prev.start <= x.start; });
 		if (pool.empty()) pool.push_back(0);
-		std::vector<int64_t> tb0((size_t)n_ref + 1, 0); std::vector<int32_t> bucket;   // 64 kb buckets as in the site pileup: bucket -> first window starting at or behind it
-		for (int r = 0; r < n_ref; ++r)
-		{
-			tb0[(size_t)r] = (int64_t)bucket.size();
-			if (tf[(size_t)r] >= tl[(size_t)r]) continue;
-			const int64_t nb = (std::max<int64_t>(h->ref_lens[(size_t)r], start[(size_t)tl[(size_t)r] - 1]) >> PILEUP_BUCKET_SHIFT) + 2;
-			int32_t i = tf[(size_t)r];
-			for (int64_t b = 0; b < nb; ++b) { const int64_t lo = b << PILEUP_BUCKET_SHIFT; while (i < tl[(size_t)r] && start[(size_t)i] < lo) ++i; bucket.push_back(i); }
-		}
-		tb0[(size_t)n_ref] = (int64_t)bucket.size();
-		if (bucket.empty()) bucket.push_back(0);
-		d_start.upload(start, h->stream); d_win.upload(win, h->stream); d_pool.upload(pool, h->stream); d_tf.upload(tf, h->stream); d_tl.upload(tl, h->stream);
-		d_maxlen.upload(maxlen, h->stream); d_bucket.upload(bucket, h->stream); d_tb0.upload(tb0, h->stream);
+		tab.upload(h, pt); d_win.upload(win, h->stream); d_pool.upload(pool, h->stream); d_maxlen.upload(maxlen, h->stream);
 		d_cnt.ensure((size_t)n * 8); d_nlong.ensure(1);
 		HIPCHK(hipMemsetAsync(d_cnt.p, 0, (size_t)n * 8 * sizeof(uint32_t), h->stream));
 		HIPCHK(hipStreamSynchronize(h->stream));   // (the staging vectors go out of scope)
-		t.start = d_start.p; t.win = d_win.p; t.pool = d_pool.p; t.tid_first = d_tf.p; t.tid_last = d_tl.p; t.tid_maxlen = d_maxlen.p; t.bucket = d_bucket.p; t.tid_bucket0 = d_tb0.p;
+		t.tab = tab.view(); t.win = d_win.p; t.pool = d_pool.p; t.tid_maxlen = d_maxlen.p;
 		t.n_ref = n_ref; t.include_npp = npp ? 1 : 0;
 	}
 	void tile(ngsqc_handle* h, const TileCtx& c)

@@ -429,16 +429,14 @@ __device__ __forceinline__ void pile_candidate(const ScanParams& p, const RecVie
 	if (a.pc_tid != r.tid || start1 <= a.pc_lo || start1 > a.pc_next)
 	{
 		// the first site at or behind start1 (and the one in front of it): they answer every record that starts between them; a reference without sites: never
-		const int first = p.pile.tid_first[r.tid], last = p.pile.tid_last[r.tid];
+		const PosTable& t = p.pile.sites;
+		const int first = t.tid_first[r.tid], last = t.tid_last[r.tid];
 		a.pc_tid = r.tid; a.pc_lo = INT32_MIN; a.pc_next = INT32_MAX;
 		if (first < last)
 		{
-			const int64_t b0 = p.pile.tid_bucket0[r.tid], nbk = p.pile.tid_bucket0[r.tid + 1] - b0;
-			int64_t bi = start1 > 0 ? (int64_t)(start1 >> PILEUP_BUCKET_SHIFT) : 0; if (bi >= nbk) bi = nbk - 1;
-			int i = p.pile.bucket[b0 + bi];
-			while (i < last && p.pile.site_pos[i] < start1) ++i;
-			if (i < last) a.pc_next = p.pile.site_pos[i];
-			if (i > first) a.pc_lo = p.pile.site_pos[i - 1];
+			const int i = postable_lower_scan(t, r.tid, last, start1);
+			if (i < last) a.pc_next = t.pos[i];
+			if (i > first) a.pc_lo = t.pos[i - 1];
 		}
 		settle_loads();
 	}
@@ -1099,9 +1097,7 @@ __device__ static int pileup_base(const RecView& r, int pos, int& qual_out)   //
 }
 
 __global__ __launch_bounds__(256) void pileup_kernel(const uint8_t* __restrict__ infl, const int64_t* __restrict__ recoff, long long n_rec, int n_ref,
-                                                     const int32_t* __restrict__ site_pos, const int32_t* __restrict__ tid_first, const int32_t* __restrict__ tid_last,
-                                                     const int32_t* __restrict__ bucket, const int64_t* __restrict__ tid_bucket0,
-                                                     int min_mapq, int min_baseq, int include_npp, uint32_t* __restrict__ counts,
+                                                     const PosTable sites, int min_mapq, int min_baseq, int include_npp, uint32_t* __restrict__ counts,
                                                      int64_t* __restrict__ long_list, unsigned long long* __restrict__ long_count)
 {
 	for (long long li = (long long)blockIdx.x * blockDim.x + threadIdx.x; li < n_rec; li += (long long)gridDim.x * blockDim.x)
@@ -1112,7 +1108,7 @@ __global__ __launch_bounds__(256) void pileup_kernel(const uint8_t* __restrict__
 		if (!(flag & 0x2) && !include_npp) continue;                         // :831
 		if ((int)r.mapq < min_mapq) continue;                                // :836
 		if (r.tid < 0 || r.tid >= n_ref) continue;
-		const int first = tid_first[r.tid], last = tid_last[r.tid];
+		const int first = sites.tid_first[r.tid], last = sites.tid_last[r.tid];
 		if (first >= last) continue;
 		rec_apply_cg(r);   // CG:B,I long CIGAR
 		if (r.n_cigar > (uint32_t)LONG_CIGAR) { long_list[atomicAdd(long_count, 1ull)] = li; continue; }   // wave-per-record path (pileup_long_kernel)
@@ -1120,12 +1116,8 @@ __global__ __launch_bounds__(256) void pileup_kernel(const uint8_t* __restrict__
 		for (uint32_t k = 0; k < r.n_cigar; ++k) { const uint32_t c = ld32(r.cigar + 4ull * k); if ((0x18Du >> (c & 15u)) & 1u) ref_len += c >> 4; }
 		if (ref_len == 0) ref_len = 1;                                        // bam_endpos
 		const int start1 = r.pos + 1, end1 = (int)(r.pos + ref_len);
-		// first site with pos >= start1: bucket[tid][start1 >> 16] = first site at or behind the bucket's first position, then a short scan
-		const int64_t b0 = tid_bucket0[r.tid], nbk = tid_bucket0[r.tid + 1] - b0;
-		int64_t bi = start1 > 0 ? (int64_t)(start1 >> PILEUP_BUCKET_SHIFT) : 0; if (bi >= nbk) bi = nbk - 1;
-		int a = bucket[b0 + bi];
-		while (a < last && site_pos[a] < start1) ++a;
-		for (int i = a; i < last && site_pos[i] <= end1; ++i)
+		const int32_t* __restrict__ site_pos = sites.pos;
+		for (int i = postable_lower_scan(sites, r.tid, last, start1); i < last && site_pos[i] <= end1; ++i)
 		{
 			int q; const int base = pileup_base(r, site_pos[i], q);
 			if (base == -2) atomicAdd(&counts[8ull * i + 7], 1u);
@@ -1143,9 +1135,7 @@ __global__ __launch_bounds__(256) void pileup_kernel(const uint8_t* __restrict__
 // exhausts the read in front of that operation ends the walk for this and every later site (:346-353), and so does an operation the reference throws on (P or a
 // code above 8, :357-360: column 7 for them), whichever of the two comes first in the CIGAR. The stream ends behind the last site of the span.
 __global__ __launch_bounds__(256) void pileup_long_kernel(const uint8_t* __restrict__ infl, const int64_t* __restrict__ recoff, const int64_t* __restrict__ long_list, const unsigned long long* __restrict__ n_long_dev,
-                                                          const int32_t* __restrict__ site_pos, const int32_t* __restrict__ tid_last,
-                                                          const int32_t* __restrict__ bucket, const int64_t* __restrict__ tid_bucket0,
-                                                          int min_baseq, uint32_t* __restrict__ counts)
+                                                          const PosTable sites, int min_baseq, uint32_t* __restrict__ counts)
 {
 	const int lane = threadIdx.x & 63;
 	const long long wave = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = ((long long)gridDim.x * blockDim.x) >> 6;
@@ -1185,11 +1175,9 @@ __global__ __launch_bounds__(256) void pileup_long_kernel(const uint8_t* __restr
 		ref_len = wave_sum(ref_len);
 		if (ref_len == 0) ref_len = 1;   // bam_endpos
 		const int start1 = r.pos + 1, end1 = (int)(r.pos + ref_len);
-		const int last = tid_last[r.tid];
-		const int64_t b0 = tid_bucket0[r.tid], nbk = tid_bucket0[r.tid + 1] - b0;
-		int64_t bi = start1 > 0 ? (int64_t)(start1 >> PILEUP_BUCKET_SHIFT) : 0; if (bi >= nbk) bi = nbk - 1;
-		int cur = bucket[b0 + bi];
-		while (cur < last && site_pos[cur] < start1) ++cur;
+		const int32_t* __restrict__ site_pos = sites.pos;
+		const int last = sites.tid_last[r.tid];
+		int cur = postable_lower_scan(sites, r.tid, last, start1);
 		int site_end = cur; while (site_end < last && site_pos[site_end] <= end1) ++site_end;
 		if (cur >= site_end) continue;
 		// ---- pass 2: the operations in order ----
@@ -1241,20 +1229,19 @@ __global__ __launch_bounds__(256) void pileup_long_kernel(const uint8_t* __restr
 	}
 }
 
-void launch_pileup(const uint8_t* infl, const int64_t* recoff, int64_t n_rec, int n_ref, const int32_t* site_pos, const int32_t* tid_first, const int32_t* tid_last,
-                   const int32_t* bucket, const int64_t* tid_bucket0, int min_mapq, int min_baseq, int include_npp, uint32_t* counts,
+void launch_pileup(const uint8_t* infl, const int64_t* recoff, int64_t n_rec, int n_ref, const PosTable& sites, int min_mapq, int min_baseq, int include_npp, uint32_t* counts,
                    int64_t* long_list, unsigned long long* long_count, hipStream_t s)
 {
 	if (n_rec <= 0) return;
 	const int grid = (int)std::min<int64_t>((n_rec + 255) / 256, 256 * 32);
-	hipLaunchKernelGGL(pileup_kernel, dim3(grid), dim3(256), 0, s, infl, recoff, (long long)n_rec, n_ref, site_pos, tid_first, tid_last, bucket, tid_bucket0, min_mapq, min_baseq, include_npp, counts, long_list, long_count); KCHECK();
+	hipLaunchKernelGGL(pileup_kernel, dim3(grid), dim3(256), 0, s, infl, recoff, (long long)n_rec, n_ref, sites, min_mapq, min_baseq, include_npp, counts, long_list, long_count); KCHECK();
 }
-void launch_pileup_long(const uint8_t* infl, const int64_t* recoff, const int64_t* long_list, const unsigned long long* d_n_long, int64_t n_long_max, const int32_t* site_pos, const int32_t* tid_last,
-                        const int32_t* bucket, const int64_t* tid_bucket0, int min_baseq, uint32_t* counts, hipStream_t s)
+void launch_pileup_long(const uint8_t* infl, const int64_t* recoff, const int64_t* long_list, const unsigned long long* d_n_long, int64_t n_long_max, const PosTable& sites,
+                        int min_baseq, uint32_t* counts, hipStream_t s)
 {
 	if (n_long_max <= 0) return;
 	const int grid = (int)std::min<int64_t>((n_long_max + 3) / 4, 256 * 16);   // (sized for the most there can be; the waves stride over what there is)
-	hipLaunchKernelGGL(pileup_long_kernel, dim3(grid), dim3(256), 0, s, infl, recoff, long_list, d_n_long, site_pos, tid_last, bucket, tid_bucket0, min_baseq, counts); KCHECK();
+	hipLaunchKernelGGL(pileup_long_kernel, dim3(grid), dim3(256), 0, s, infl, recoff, long_list, d_n_long, sites, min_baseq, counts); KCHECK();
 }
 
 } // namespace ngsqc

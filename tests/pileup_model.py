@@ -20,7 +20,7 @@ import advbam as A
 import variant_oracle as V
 
 LONG_CIGAR = 64           # csrc/common.h: more operations -> the wave-per-record kernels
-PILEUP_BUCKET_SHIFT = 16  # csrc/common.h: 64 kb buckets of the site and window tables
+PILEUP_BUCKET_SHIFT = 16  # csrc/postable.h: 64 kb buckets of the site and window tables (the table itself on the CPU: test_cpu_postable.py)
 N_SITE_COLS, N_WIN_COLS = 8, 7
 COL = {"A": 0, "C": 1, "G": 2, "T": 3, "N": 4}
 W_MAPPED, W_MAPQ0, W_DEPTH, W_INS, W_DEL, W_MATCH, W_UNKNOWN = range(7)
